@@ -3,8 +3,13 @@
 convnet trained with AllReduceSGD (BASELINE.json "metric"), bf16 compute,
 synthetic CIFAR-shaped data, random-init weights.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints one JSON line.
+``--dump-outputs DIR`` also writes what the last timed step left (loss,
+parameters, log-probabilities) as ``DIR/<name>.npy``; ``--full`` adds the
+measurements that take runs of their own (the communication profile).
 
 With ``--gpus N > 1`` and no torch.distributed environment (WORLD_SIZE
 unset), bench.py launches itself: the parent spawns N child processes (one
@@ -82,7 +87,46 @@ def parse():
     ap.add_argument("--launch-timeout", type=float, default=1800.0,
                     help="self-launch (--gpus N > 1 without torch.distributed.run): seconds before the children "
                          "are killed and bench.py exits non-zero")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the measurements that need runs of their own, outside the timed region: the "
+                         "communication profile (`comm`) of N > 1 and --nworld-path runs.  Off by default: a plain "
+                         "run sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step left to DIR/<name>.npy (float32): "
+                         "loss.npy (the step's loss), params.npy (the flat parameter vector after the update; "
+                         "a fixed seeded sample of it when it exceeds the 64 MB budget) and logits.npy (the step's "
+                         "log-probabilities, [batch, classes]).  Written by the first training rank.  Unless "
+                         "DISTLEARN_REDUCE_ATOMIC is set, such a run takes the CIFAR-10 executor's deterministic "
+                         "reduction mode 0 (partial rows + finalize kernels, bitwise reproducible) and says so on "
+                         "stderr: its value and ms_per_step are that mode's, about 7 %% slower than the default "
+                         "fp32-atomic mode 2 of a run without this option, whose last-bit differences a few bf16 "
+                         "training steps amplify to per cent.  DISTLEARN_REDUCE_ATOMIC=2 dumps the default mode; "
+                         "the result line's config.reduce_mode says which mode ran")
     return ap.parse_args()
+
+
+DUMP_BUDGET = 60 << 20  # bytes of float32 per --dump-outputs directory (limit 64 MB)
+
+
+def _dump_outputs(path, loss, params, logp=None) -> None:
+    """``loss``, the flat parameter vector after the last timed step and that
+    step's log-probabilities as float32 ``.npy`` files; parameters beyond the
+    budget are cut to a fixed sample (sorted indices of a permutation seeded
+    with 0)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    p = params.detach().reshape(-1)
+    keep = DUMP_BUDGET // 4
+    if p.numel() > keep:
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randperm(p.numel(), generator=g)[:keep].sort().values
+        p = p[idx.to(p.device)]
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    np.save(os.path.join(path, "params.npy"), p.float().cpu().numpy())
+    if logp is not None:  # [batch, classes]: a few KB
+        np.save(os.path.join(path, "logits.npy"), logp.detach().float().cpu().numpy())
 
 
 def _self_launch(a) -> int:
@@ -195,6 +239,18 @@ def main():
         print("bench.py: --algo async needs >= 2 ranks (1 server + clients)", file=sys.stderr)
         sys.exit(2)
     cpu = a.device == "cpu"
+    if a.dump_outputs:
+        # outputs that two runs (or two builds) can be compared by: the executor's
+        # deterministic reductions.  The default mode 2 sums the BatchNorm statistics
+        # with fp32 atomics, and the steps amplify its last-bit differences (two runs:
+        # 2e-6 of the parameters after 1 step, 1e-3 after 2, 5e-2 after 25).
+        # DISTLEARN_REDUCE_ATOMIC=2 --dump-outputs DIR dumps the default mode instead
+        if "DISTLEARN_REDUCE_ATOMIC" not in os.environ:
+            os.environ["DISTLEARN_REDUCE_ATOMIC"] = "0"
+            if rank == 0 and a.model == "cifar10" and not cpu:
+                print("bench.py: --dump-outputs: deterministic reduction mode 0 (reproducible outputs); value and "
+                      "ms_per_step are this mode's, about 7 % slower than the default mode 2 of a run without "
+                      "--dump-outputs (DISTLEARN_REDUCE_ATOMIC=2 dumps that mode)", file=sys.stderr)
     if a.nworld_path:
         if world != 1 or cpu:
             print("bench.py: --nworld-path rehearses the multi-node step on ONE GPU", file=sys.stderr)
@@ -307,8 +363,8 @@ def main():
         if step_args is None:
             tr.prepare(loader, unroll)  # (run() already did; explicit: no capture may fall in the timed region)
         comm = {}
-        if (len(workers) > 1 or a.nworld_path) and a.algo == "sgd" and not cpu:
-            # communication profile: HIP events around every bucket all-reduce, read from
+        if a.full and (len(workers) > 1 or a.nworld_path) and a.algo == "sgd" and not cpu:
+            # --full: communication profile, HIP events around every bucket all-reduce, read from
             # replays of a captured one-step graph (the timed schedule; eager steps when
             # the model has no device loader), OUTSIDE the timed region; training state
             # is restored after
@@ -370,6 +426,10 @@ def main():
         if tr.captures != captures0:
             raise RuntimeError(f"bench.py: {tr.captures - captures0} hipGraph capture(s) inside the timed region")
         tr.finish()
+        if a.dump_outputs and rank == workers[0]:
+            # (the PyTorch step keeps its log-probabilities in _last_logp, once it has run)
+            keeps_logp = getattr(tr, "executor", None) is not None or hasattr(tr, "_last_logp")
+            _dump_outputs(a.dump_outputs, loss, tr.flat.data, tr.last_logits() if keeps_logp else None)
     # max over ranks (the AsyncEA server contributes 0); loss from the first worker
     t = torch.tensor([dt, float(loss.float().item()) if (loss is not None and rank == workers[0]) else -1e30],
                      dtype=torch.float64)
@@ -391,6 +451,8 @@ def main():
         "channel_cap": getattr(tree.comm, "channel_cap", None),
         "cu_reserve": getattr(ex, "cu_reserve", None),
         "dgrad_stages": getattr(ex, "dgrad_stages", None),
+        # 2 = fp32-atomic reductions (default), 0 = deterministic (--dump-outputs runs)
+        "reduce_mode": getattr(ex, "mode", None),
         # the wire dtype actually used (world 1: no collective, fp32)
         "grad_comm_dtype": getattr(tr, "grad_comm_dtype", "fp32") if not is_server else "fp32",
         "delta_wire": a.grad_comm_dtype if a.algo == "async" else None,

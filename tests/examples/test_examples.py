@@ -136,6 +136,34 @@ def test_bench_self_launch_cpu():
     assert out["config"]["grad_comm_dtype"] == "fp32" and "device_ids" in out["config"]
 
 
+def test_bench_dump_outputs_repeatable_cpu(tmp_path):
+    """``--dump-outputs DIR``: float32 ``.npy`` files of what the last timed
+    step left; the inputs are seeded, so two runs with the same arguments (CPU:
+    no atomics) write identical files.  ``--full`` changes no output."""
+    import json
+
+    import numpy as np
+
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--device", "cpu", "--gpus", "1", "--steps", "2",
+               "--warmup", "1", "--batch", "4", "--dump-outputs", str(tmp_path / name)] + extra
+        env = dict(os.environ, PYTHONPATH=ROOT, OMP_NUM_THREADS="1")
+        env.pop("WORLD_SIZE", None)
+        r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+        got = {f: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))}
+        assert sorted(got) == ["logits.npy", "loss.npy", "params.npy"]
+        assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in got.values())
+        assert got["logits.npy"].shape == (4, 10) and got["params.npy"].shape == (4329088,)
+        assert abs(float(got["loss.npy"][0]) - rec["final_loss"]) <= 1e-4
+        dumps.append(got)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
+
 def test_bench_self_launch_fails_fast_without_gpus():
     """``--gpus 2`` on a box with fewer GPUs: every rank exits with a clear
     message before any rendezvous and the launcher returns non-zero at once."""

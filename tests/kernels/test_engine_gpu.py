@@ -265,6 +265,87 @@ def test_bench_json_contract(dev, algo):
     assert rec["n_gpus"] == 1 and rec["steps"] == 5 and rec["value"] > 0 and rec["dtype"] == "bf16"
 
 
+def _bench_dump(out_dir, mode=None, args=("--steps", "1", "--warmup", "0")):
+    """One ``bench.py --gpus 1 --dump-outputs`` run with DISTLEARN_REDUCE_ATOMIC
+    unset (``mode`` None) or set: (result record, {file: array}, stderr)."""
+    import numpy as np
+
+    env = {k: v for k, v in os.environ.items() if k != "DISTLEARN_REDUCE_ATOMIC"}
+    env["PYTHONPATH"] = ROOT
+    if mode is not None:
+        env["DISTLEARN_REDUCE_ATOMIC"] = str(mode)
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", *args, "--dump-outputs", str(out_dir)], cwd=ROOT,
+                       env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    rec = json.loads(r.stdout.strip().splitlines()[-1])
+    return rec, {f: np.load(os.path.join(out_dir, f)) for f in sorted(os.listdir(out_dir))}, r.stderr
+
+
+@pytest.fixture(scope="module")
+def bench_dump(dev, tmp_path_factory):
+    """The dump of one benchmark step with no reduction mode in the environment
+    (shared, read-only)."""
+    return _bench_dump(tmp_path_factory.mktemp("dump") / "o")
+
+
+def test_bench_dump_outputs(dev, bench_dump, tmp_path):
+    """--dump-outputs writes what the last timed step left as float32 .npy
+    files: its loss (the result line's final_loss), the flat parameter vector
+    (4.33M floats, inside the 64 MB budget unsampled) and the batch's
+    log-probabilities (rows sum to 1 in probability).  With no reduction mode
+    in the environment such a run takes the deterministic one by itself and
+    says so: two runs with the same arguments write bitwise identical files."""
+    import numpy as np
+
+    rec, got, err = bench_dump
+    assert "comm" not in rec  # measurements beyond the headline are behind --full
+    assert rec["config"]["reduce_mode"] == 0 and "deterministic reduction mode 0" in err
+    rec2, again, _ = _bench_dump(tmp_path / "p")
+    assert sorted(got) == sorted(again) == ["logits.npy", "loss.npy", "params.npy"]
+    for f in got:
+        assert np.array_equal(got[f], again[f]), f
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+    assert got["loss.npy"].shape == (1,) and abs(float(got["loss.npy"][0]) - rec["final_loss"]) <= 1e-4
+    assert got["params.npy"].shape == (4329088,) and float(np.abs(got["params.npy"]).max()) > 0
+    assert got["logits.npy"].shape == (128, 10)
+    np.testing.assert_allclose(np.exp(got["logits.npy"].astype(np.float64)).sum(1), 1.0, atol=1e-3)  # fp32 log-softmax
+
+
+def test_bench_dump_default_mode(dev, bench_dump, tmp_path):
+    """DISTLEARN_REDUCE_ATOMIC=2 --dump-outputs dumps the default (fp32-atomic)
+    reduction mode, the one a run without the option times.  One step from the
+    same seeded state differs from the deterministic mode only in the order of
+    fp32 sums (BatchNorm statistics and parameter gradients), which can flip
+    roundings of the step's bf16 operands: each output stays within one bf16
+    rounding (2^-8) of the other mode's, in norm.  (Two mode-2 runs of one
+    step measured 2e-6 of the parameters apart; more steps amplify that.)"""
+    import numpy as np
+
+    _, ref, _ = bench_dump
+    rec, got, err = _bench_dump(tmp_path / "m2", mode=2)
+    assert rec["config"]["reduce_mode"] == 2 and "deterministic reduction mode" not in err
+    assert sorted(got) == sorted(ref)
+    for f in got:
+        a, b = got[f].astype(np.float64), ref[f].astype(np.float64)
+        d = float(np.linalg.norm(a - b) / np.linalg.norm(b))
+        print(f"{f}: mode 2 vs mode 0, relative difference {d:.3g}")
+        assert got[f].dtype == np.float32 and a.shape == b.shape and d <= 2.0 ** -8, (f, d)
+
+
+def test_bench_full_reports_comm(dev):
+    """--full brings back what a plain run leaves out: the communication
+    profile of the multi-node step configuration (--nworld-path 1), read from
+    graph replays outside the timed region.  (The overlap policy is forced:
+    timing its candidates is not what this test is about.)"""
+    args = ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2", "--nworld-path", "1", "--full"]
+    rec = json.loads(_run(args, env={"DISTLEARN_POLICY": "full"}).strip().splitlines()[-1])
+    comm = rec["comm"]
+    assert comm["buckets"] == 3 and comm["bytes_per_step"] == 4329088 * 4 and comm["steps"] == 6
+    assert comm["comm_ms"] > 0 and 0.0 <= comm["overlap_fraction"] <= 1.0
+    assert rec["steps"] == 5 and rec["ms_per_step"] > 0
+
+
 def test_run_captures_only_before_timed_steps(dev):
     """trainer.run captures the single-step and the unrolled graph before the
     first step, whatever nsteps is (the driver's --warmup 5 < unroll 8 case):
