@@ -15,7 +15,9 @@ PYBIND11_MODULE(_C, m) {
 
   // ---- flat bucket kernels --------------------------------------------------
   m.def("sgd_update", &sgd_update, py::arg("p"), py::arg("g"), py::arg("mom"), py::arg("p16"), py::arg("slot"),
-        py::arg("lr"), py::arg("momentum"), py::arg("wd"), py::arg("n"), py::arg("stream"));
+        py::arg("lr"), py::arg("momentum"), py::arg("wd"), py::arg("n"), py::arg("stream"), py::arg("lr_dev") = 0);
+  m.def("lr_ring_set", &lr_ring_set, py::arg("ring"), py::arg("ring_len"), py::arg("offset"), py::arg("vals"),
+        py::arg("stream"));
   m.def("scale_by_count", &scale_by_count);
   m.def("elastic_step", &elastic_step);
   m.def("elastic_step_wire16", &elastic_step_wire16);
@@ -25,13 +27,21 @@ PYBIND11_MODULE(_C, m) {
   m.def("stamp_time", &stamp_time);
   m.def("wall_clock_khz", &wall_clock_khz);
   m.def("cast_bf16_f32", &cast_bf16_f32);
-  m.def("sgd_update_g16", &sgd_update_g16);
-  m.def("sgd_update_slabs", &sgd_update_slabs);
+  m.def("sgd_update_g16", &sgd_update_g16, py::arg("p"), py::arg("g16"), py::arg("mom"), py::arg("p16"),
+        py::arg("slot"), py::arg("lr"), py::arg("momentum"), py::arg("wd"), py::arg("n"), py::arg("stream"),
+        py::arg("lr_dev") = 0);
+  m.def("sgd_update_slabs", &sgd_update_slabs, py::arg("p"), py::arg("g"), py::arg("mom"), py::arg("p16"),
+        py::arg("slot"), py::arg("lr"), py::arg("momentum"), py::arg("wd"), py::arg("n"), py::arg("offs"),
+        py::arg("lens"), py::arg("slabs"), py::arg("splits"), py::arg("tail"), py::arg("tail_slab"),
+        py::arg("skip_lo"), py::arg("skip_hi"), py::arg("stream"), py::arg("lr_dev") = 0);
   m.def("arm_sgd_next_prep", &arm_sgd_next_prep);
   m.def("sgd_next_prep_armed", &sgd_next_prep_armed);
   m.def("set_sgd_trim", &set_sgd_trim);
   m.def("disarm_sgd_next_prep", &disarm_sgd_next_prep);
-  m.def("set_conv_side_sgd", &set_conv_side_sgd);
+  m.def("set_conv_side_sgd", &set_conv_side_sgd, py::arg("p"), py::arg("g"), py::arg("mom"), py::arg("p16"),
+        py::arg("slot"), py::arg("lr"), py::arg("momentum"), py::arg("wd"), py::arg("lo"), py::arg("hi"),
+        py::arg("offs"), py::arg("lens"), py::arg("slabs"), py::arg("splits"), py::arg("nblk"),
+        py::arg("lr_dev") = 0);
   m.def("set_conv_side_reduce", &set_conv_side_reduce);
   m.def("slab_reduce_multi", &slab_reduce_multi);
   m.def("confusion_update", &confusion_update);

@@ -9,8 +9,12 @@
 namespace dl {
 
 // flat_ops.hip -------------------------------------------------------------
+// lr_dev (every update below): 0, or a device fp32 the kernels read the learning
+// rate from instead of the immediate lr (a schedule inside a replayed hipGraph)
 void sgd_update(uintptr_t p, uintptr_t g, uintptr_t mom, uintptr_t p16, uintptr_t slot, float lr, float momentum,
-                float wd, int64_t n, uintptr_t stream);
+                float wd, int64_t n, uintptr_t stream, uintptr_t lr_dev = 0);
+// ring[offset .. offset + vals.size()) = vals (1..32 fp32 values, one small launch)
+void lr_ring_set(uintptr_t ring, int64_t ring_len, int64_t offset, std::vector<float> vals, uintptr_t stream);
 void scale_by_count(uintptr_t x, uintptr_t slot, int64_t n, uintptr_t stream);
 void elastic_step(uintptr_t p, uintptr_t c, uintptr_t pending, uintptr_t out, uintptr_t p16, float alpha, int64_t n,
                   uintptr_t stream);
@@ -26,13 +30,14 @@ void cast_bf16_f32(uintptr_t x, uintptr_t y, int64_t n, uintptr_t stream);
 // as nblk extra workgroups (conv_igemm.hip; flat_ops' update then skips them)
 void set_conv_side_sgd(uintptr_t p, uintptr_t g, uintptr_t mom, uintptr_t p16, uintptr_t slot, float lr,
                        float momentum, float wd, int64_t lo, int64_t hi, std::vector<int64_t> offs,
-                       std::vector<int64_t> lens, std::vector<uintptr_t> slabs, std::vector<int> splits, int nblk);
+                       std::vector<int64_t> lens, std::vector<uintptr_t> slabs, std::vector<int> splits, int nblk,
+                       uintptr_t lr_dev = 0);
 // ... or sums split-K weight-gradient slabs into the gradient buffer g instead
 // (reduce-only side job: a multi-node step's gradients before the all-reduce)
 void set_conv_side_reduce(uintptr_t g, int64_t lo, int64_t hi, std::vector<int64_t> offs, std::vector<int64_t> lens,
                           std::vector<uintptr_t> slabs, std::vector<int> splits, int nblk);
 void sgd_update_g16(uintptr_t p, uintptr_t g16, uintptr_t mom, uintptr_t p16, uintptr_t slot, float lr,
-                    float momentum, float wd, int64_t n, uintptr_t stream);
+                    float momentum, float wd, int64_t n, uintptr_t stream, uintptr_t lr_dev = 0);
 // sgd_update whose gradient in up to 4 ranges [offs, offs+lens) is the sum of the
 // split-K slabs [splits][lens] at slabs[j], and in one optional channel-padded
 // "tail" range (offset, numel, splits, Cout, taps, Cp, C) the sum of tail_slab
@@ -41,7 +46,8 @@ void sgd_update_g16(uintptr_t p, uintptr_t g16, uintptr_t mom, uintptr_t p16, ui
 void sgd_update_slabs(uintptr_t p, uintptr_t g, uintptr_t mom, uintptr_t p16, uintptr_t slot, float lr,
                       float momentum, float wd, int64_t n, std::vector<int64_t> offs, std::vector<int64_t> lens,
                       std::vector<uintptr_t> slabs, std::vector<int> splits, std::vector<int64_t> tail,
-                      uintptr_t tail_slab, int64_t skip_lo, int64_t skip_hi, uintptr_t stream);
+                      uintptr_t tail_slab, int64_t skip_lo, int64_t skip_hi, uintptr_t stream,
+                      uintptr_t lr_dev = 0);
 // one-shot: the next sgd_update_slabs launch also prepares the next step of an
 // unrolled graph -- gathers its batch into xp, zeroes its accumulators (prep_dev.h)
 // and writes the first layer's updated weights into the packed bf16 operand w1p

@@ -2573,11 +2573,13 @@ int conv_fwd(uintptr_t x, uintptr_t w, uintptr_t y, uintptr_t stats, uintptr_t s
 // elements [lo, hi) of the flat buffer p (gradient g, or the split-K slabs of
 // the given ranges; bf16 shadow p16 required) as nblk extra workgroups
 // (0: one float4 per thread).  One-shot; the caller's final update skips [lo, hi).
+// lr_dev != 0: the rate is read from that device fp32 instead of lr (sgd_dev.h sgd_rate).
 void set_conv_side_sgd(uintptr_t p, uintptr_t g, uintptr_t mom, uintptr_t p16, uintptr_t slot, float lr,
                        float momentum, float wd, int64_t lo, int64_t hi, std::vector<int64_t> offs,
-                       std::vector<int64_t> lens, std::vector<uintptr_t> slabs, std::vector<int> splits, int nblk) {
+                       std::vector<int64_t> lens, std::vector<uintptr_t> slabs, std::vector<int> splits, int nblk,
+                       uintptr_t lr_dev) {
   if (!p16) throw std::runtime_error("set_conv_side_sgd: needs the bf16 shadow");
-  SgdJob j = make_sgd_job(p, g, mom, p16, slot, lr, momentum, wd, lo, hi, offs, lens, slabs, splits, {}, 0);
+  SgdJob j = make_sgd_job(p, g, mom, p16, slot, lr, momentum, wd, lo, hi, offs, lens, slabs, splits, {}, 0, lr_dev);
   j.nblk = nblk > 0 ? nblk : -1;  // -1: sized by the launch (one float4 per thread)
   g_side_sgd = j;
 }

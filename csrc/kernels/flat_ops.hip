@@ -29,9 +29,10 @@ namespace dl {
 template <bool kMomentum, bool kShadow, typename GT = float>
 __global__ void __launch_bounds__(256) sgd_kernel(float* __restrict__ p, const GT* __restrict__ g,
                                                   float* __restrict__ mom, bf16_t* __restrict__ p16,
-                                                  const float* __restrict__ slot, float lr, float momentum,
-                                                  float wd, int64_t n4) {
+                                                  const float* __restrict__ slot, float lr_imm, float momentum,
+                                                  float wd, int64_t n4, const float* __restrict__ lr_dev) {
   const float s = participation_scale(slot);
+  const float lr = sgd_rate(lr_dev, lr_imm);
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   auto update = [&](int64_t i, float4 pv, const float4 gv, float4 mv) {
     pv = sgd_elem4<kMomentum>(pv, gv, mv, s, wd, lr, momentum);
@@ -227,6 +228,18 @@ __global__ void __launch_bounds__(64) stamp_kernel(long long* __restrict__ slot)
   }
 }
 
+// Up to 32 learning rates, passed by value in the kernel arguments (no host
+// staging buffer has to outlive a host that runs many replays ahead), written
+// into the device ring the update kernels of a captured step read (sgd_rate).
+constexpr int kLrSetMax = 32;
+struct LrVals {
+  float v[kLrSetMax];
+};
+__global__ void __launch_bounds__(64) lr_ring_set_kernel(float* __restrict__ ring, const LrVals vals, int n) {
+  const int t = (int)threadIdx.x;
+  if (t < n) ring[t] = vals.v[t];
+}
+
 // ---------------------------------------------------------------------------
 // Host launchers (C ABI-ish, raw pointers + stream handle)
 // ---------------------------------------------------------------------------
@@ -234,19 +247,25 @@ static void check_vec4(int64_t n, const char* what) {
   if (n % 4 != 0) throw std::runtime_error(std::string(what) + ": element count must be a multiple of 4");
 }
 
+static const float* check_lr_dev(uintptr_t lr_dev, const char* what) {
+  if (lr_dev % 4) throw std::runtime_error(std::string(what) + ": the device learning rate must be a 4-byte aligned fp32");
+  return (const float*)lr_dev;
+}
+
 void sgd_update(uintptr_t p, uintptr_t g, uintptr_t mom, uintptr_t p16, uintptr_t slot, float lr, float momentum,
-                float wd, int64_t n, uintptr_t stream) {
+                float wd, int64_t n, uintptr_t stream, uintptr_t lr_dev) {
   check_vec4(n, "sgd_update");
+  const float* LR = check_lr_dev(lr_dev, "sgd_update");
   const int64_t n4 = n / 4;
   if (n4 == 0) return;
   dim3 grid(stream_grid(n4)), block(256);
   auto s = as_stream(stream);
   float* P = (float*)p; const float* G = (const float*)g; float* M = (float*)mom; bf16_t* P16 = (bf16_t*)p16;
   const float* S = (const float*)slot;
-  if (mom && p16) sgd_kernel<true, true><<<grid, block, 0, s>>>(P, G, M, P16, S, lr, momentum, wd, n4);
-  else if (mom) sgd_kernel<true, false><<<grid, block, 0, s>>>(P, G, M, P16, S, lr, momentum, wd, n4);
-  else if (p16) sgd_kernel<false, true><<<grid, block, 0, s>>>(P, G, M, P16, S, lr, momentum, wd, n4);
-  else sgd_kernel<false, false><<<grid, block, 0, s>>>(P, G, M, P16, S, lr, momentum, wd, n4);
+  if (mom && p16) sgd_kernel<true, true><<<grid, block, 0, s>>>(P, G, M, P16, S, lr, momentum, wd, n4, LR);
+  else if (mom) sgd_kernel<true, false><<<grid, block, 0, s>>>(P, G, M, P16, S, lr, momentum, wd, n4, LR);
+  else if (p16) sgd_kernel<false, true><<<grid, block, 0, s>>>(P, G, M, P16, S, lr, momentum, wd, n4, LR);
+  else sgd_kernel<false, false><<<grid, block, 0, s>>>(P, G, M, P16, S, lr, momentum, wd, n4, LR);
   DL_HIP_CHECK(hipGetLastError());
 }
 
@@ -294,9 +313,10 @@ void disarm_sgd_next_prep() { g_next_armed = false; }
 void sgd_update_slabs(uintptr_t p, uintptr_t g, uintptr_t mom, uintptr_t p16, uintptr_t slot, float lr,
                       float momentum, float wd, int64_t n, std::vector<int64_t> offs, std::vector<int64_t> lens,
                       std::vector<uintptr_t> slabs, std::vector<int> splits, std::vector<int64_t> tail,
-                      uintptr_t tail_slab, int64_t skip_lo, int64_t skip_hi, uintptr_t stream) {
+                      uintptr_t tail_slab, int64_t skip_lo, int64_t skip_hi, uintptr_t stream, uintptr_t lr_dev) {
   check_vec4(n, "sgd_update_slabs");
-  SgdJob job = make_sgd_job(p, g, mom, p16, slot, lr, momentum, wd, 0, n, offs, lens, slabs, splits, tail, tail_slab);
+  SgdJob job = make_sgd_job(p, g, mom, p16, slot, lr, momentum, wd, 0, n, offs, lens, slabs, splits, tail, tail_slab,
+                            lr_dev);
   if (skip_hi > skip_lo) {
     if (skip_lo % 4 || skip_hi % 4 || skip_lo < 0 || skip_hi > n) throw std::runtime_error("sgd_update_slabs: bad skip");
     job.skip_lo4 = skip_lo / 4;
@@ -357,18 +377,19 @@ void slab_reduce_multi(uintptr_t g, int64_t n, std::vector<int64_t> offs, std::v
 }
 
 void sgd_update_g16(uintptr_t p, uintptr_t g16, uintptr_t mom, uintptr_t p16, uintptr_t slot, float lr,
-                    float momentum, float wd, int64_t n, uintptr_t stream) {
+                    float momentum, float wd, int64_t n, uintptr_t stream, uintptr_t lr_dev) {
   check_vec4(n, "sgd_update_g16");
+  const float* LR = check_lr_dev(lr_dev, "sgd_update_g16");
   const int64_t n4 = n / 4;
   if (n4 == 0) return;
   dim3 grid(stream_grid(n4)), block(256);
   auto s = as_stream(stream);
   float* P = (float*)p; const bf16_t* G = (const bf16_t*)g16; float* M = (float*)mom; bf16_t* P16 = (bf16_t*)p16;
   const float* S = (const float*)slot;
-  if (mom && p16) sgd_kernel<true, true, bf16_t><<<grid, block, 0, s>>>(P, G, M, P16, S, lr, momentum, wd, n4);
-  else if (mom) sgd_kernel<true, false, bf16_t><<<grid, block, 0, s>>>(P, G, M, P16, S, lr, momentum, wd, n4);
-  else if (p16) sgd_kernel<false, true, bf16_t><<<grid, block, 0, s>>>(P, G, M, P16, S, lr, momentum, wd, n4);
-  else sgd_kernel<false, false, bf16_t><<<grid, block, 0, s>>>(P, G, M, P16, S, lr, momentum, wd, n4);
+  if (mom && p16) sgd_kernel<true, true, bf16_t><<<grid, block, 0, s>>>(P, G, M, P16, S, lr, momentum, wd, n4, LR);
+  else if (mom) sgd_kernel<true, false, bf16_t><<<grid, block, 0, s>>>(P, G, M, P16, S, lr, momentum, wd, n4, LR);
+  else if (p16) sgd_kernel<false, true, bf16_t><<<grid, block, 0, s>>>(P, G, M, P16, S, lr, momentum, wd, n4, LR);
+  else sgd_kernel<false, false, bf16_t><<<grid, block, 0, s>>>(P, G, M, P16, S, lr, momentum, wd, n4, LR);
   DL_HIP_CHECK(hipGetLastError());
 }
 
@@ -440,6 +461,19 @@ void cast_f32_bf16(uintptr_t x, uintptr_t y, int64_t n, uintptr_t stream) {
 
 void stamp_time(uintptr_t slot, uintptr_t stream) {
   stamp_kernel<<<1, 64, 0, as_stream(stream)>>>((long long*)slot);
+  DL_HIP_CHECK(hipGetLastError());
+}
+
+// ring[offset .. offset + vals.size()) = vals: one small launch on the stream
+// (ring_len: the ring's length in floats, for the bounds check).
+void lr_ring_set(uintptr_t ring, int64_t ring_len, int64_t offset, std::vector<float> vals, uintptr_t stream) {
+  const int64_t n = (int64_t)vals.size();
+  if (!ring || ring % 4) throw std::runtime_error("lr_ring_set: null or misaligned ring");
+  if (n < 1 || n > kLrSetMax) throw std::runtime_error("lr_ring_set: 1..32 values per launch");
+  if (offset < 0 || offset + n > ring_len) throw std::runtime_error("lr_ring_set: values outside the ring");
+  LrVals a{};
+  for (int64_t i = 0; i < n; ++i) a.v[i] = vals[(size_t)i];
+  lr_ring_set_kernel<<<1, 64, 0, as_stream(stream)>>>((float*)ring + offset, a, (int)n);
   DL_HIP_CHECK(hipGetLastError());
 }
 

@@ -19,6 +19,12 @@ __device__ __forceinline__ float participation_scale(const float* slot) {
 }
 
 
+// The step's learning rate: the immediate value, or (lr_dev set) the fp32 the
+// host put into device memory before the launch -- a replayed hipGraph whose
+// kernel arguments are frozen still follows a schedule.  A uniform plain load,
+// once per workgroup; the same fp32 either way, so the update's bits are too.
+__device__ __forceinline__ float sgd_rate(const float* lr_dev, float lr) { return lr_dev ? *lr_dev : lr; }
+
 // G16: the gradient is the bf16 all-reduced wire copy (grad_comm_dtype="bf16":
 // half the xGMI bytes; read here directly, never widened back to fp32).
 __device__ __forceinline__ float4 load_grad4(const float* g, int64_t i) {
@@ -147,6 +153,7 @@ struct SgdJob {
   bf16_t* p16;          // null: no bf16 shadow
   const float* slot;    // participation count (null: 1)
   float lr, momentum, wd;
+  const float* lr_dev;  // null: the immediate lr; else the rate is read from here (sgd_rate)
   int64_t lo4, hi4;     // float4 range
   int64_t skip_lo4, skip_hi4;  // updated elsewhere (another launch's side job); empty: -1, -1
   SlabRanges r;
@@ -187,11 +194,12 @@ __device__ __forceinline__ void pack_range4(const SgdJob& j, int64_t i, const fl
 template <bool kMomentum, bool kShadow>
 __device__ __forceinline__ void sgd_plain_loop2(const SgdJob& j, int bid, int nblk) {
   const float s = participation_scale(j.slot);
+  const float lr = sgd_rate(j.lr_dev, j.lr);
   const int64_t stride = (int64_t)nblk * blockDim.x;
   const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
   auto live = [&](int64_t i) { return i < j.hi4 && !(i >= j.skip_lo4 && i < j.skip_hi4); };
   auto finish = [&](int64_t i, float4 pv, const float4 gv, float4 mv) {
-    pv = sgd_elem4<kMomentum>(pv, gv, mv, s, j.wd, j.lr, j.momentum);
+    pv = sgd_elem4<kMomentum>(pv, gv, mv, s, j.wd, lr, j.momentum);
     if constexpr (kMomentum) reinterpret_cast<float4*>(j.mom)[i] = mv;
     reinterpret_cast<float4*>(j.p)[i] = pv;
     if constexpr (kShadow) {
@@ -229,6 +237,7 @@ __device__ __forceinline__ void sgd_range_loop(const SgdJob& j, int bid, int nbl
     return;
   }
   const float s = participation_scale(j.slot);
+  const float lr = sgd_rate(j.lr_dev, j.lr);
   const int64_t stride = (int64_t)nblk * blockDim.x;
   for (int64_t i = j.lo4 + (int64_t)bid * blockDim.x + threadIdx.x; i < j.hi4; i += stride) {
     if (i >= r.tail_lo4 && i < r.tail_hi4) continue;  // the tail blocks update these
@@ -237,7 +246,7 @@ __device__ __forceinline__ void sgd_range_loop(const SgdJob& j, int bid, int nbl
     const float4 gv = grad4_or_slabs(j.g, r, i);
     float4 mv = make_float4(0.f, 0.f, 0.f, 0.f);
     if constexpr (kMomentum) mv = reinterpret_cast<const float4*>(j.mom)[i];
-    pv = sgd_elem4<kMomentum>(pv, gv, mv, s, j.wd, j.lr, j.momentum);
+    pv = sgd_elem4<kMomentum>(pv, gv, mv, s, j.wd, lr, j.momentum);
     if constexpr (kMomentum) reinterpret_cast<float4*>(j.mom)[i] = mv;
     reinterpret_cast<float4*>(j.p)[i] = pv;
     if constexpr (kShadow) {
@@ -267,6 +276,8 @@ __device__ __forceinline__ void slab_reduce_range_loop(const SgdJob& j, int bid,
 template <bool kMomentum, bool kShadow>
 __device__ __forceinline__ void sgd_tail_block(const SgdJob& j, int bid) {
   const float s = participation_scale(j.slot);
+  // (a reduce-only job carries no rate: lr_dev is null there, make_reduce_job)
+  const float lr = sgd_rate(j.lr_dev, j.lr);
   const SlabRanges& r = j.r;
   auto upd = [&](int64_t i, int64_t, int, float gs) {
     const int64_t e = r.tail_lo + i;  // KRSC weight: element i of the reduce's output order
@@ -275,7 +286,7 @@ __device__ __forceinline__ void sgd_tail_block(const SgdJob& j, int bid) {
       return;
     }
     float mv = kMomentum ? j.mom[e] : 0.f;
-    const float pv = sgd_elem<kMomentum>(j.p[e], gs, &mv, s, j.wd, j.lr, j.momentum);
+    const float pv = sgd_elem<kMomentum>(j.p[e], gs, &mv, s, j.wd, lr, j.momentum);
     if constexpr (kMomentum) j.mom[e] = mv;
     j.p[e] = pv;
     if constexpr (kShadow) j.p16[e] = f32_to_bf16(pv);
@@ -299,7 +310,9 @@ __device__ __forceinline__ void sgd_tail_block(const SgdJob& j, int bid) {
 inline SgdJob make_sgd_job(uintptr_t p, uintptr_t g, uintptr_t mom, uintptr_t p16, uintptr_t slot, float lr,
                            float momentum, float wd, int64_t lo, int64_t hi, const std::vector<int64_t>& offs,
                            const std::vector<int64_t>& lens, const std::vector<uintptr_t>& slabs,
-                           const std::vector<int>& splits, const std::vector<int64_t>& tail, uintptr_t tail_slab) {
+                           const std::vector<int>& splits, const std::vector<int64_t>& tail, uintptr_t tail_slab,
+                           uintptr_t lr_dev = 0) {
+  if (lr_dev % 4) throw std::runtime_error("sgd job: the device learning rate must be a 4-byte aligned fp32");
   const size_t k = offs.size();
   if (k > (size_t)kSlabRanges || lens.size() != k || slabs.size() != k || splits.size() != k)
     throw std::runtime_error("sgd job: up to 4 consistent slab ranges");
@@ -307,6 +320,7 @@ inline SgdJob make_sgd_job(uintptr_t p, uintptr_t g, uintptr_t mom, uintptr_t p1
   SgdJob j{};
   j.p = (float*)p; j.g = (const float*)g; j.mom = (float*)mom; j.p16 = (bf16_t*)p16; j.slot = (const float*)slot;
   j.lr = lr; j.momentum = momentum; j.wd = wd;
+  j.lr_dev = (const float*)lr_dev;
   j.lo4 = lo / 4; j.hi4 = hi / 4;
   j.skip_lo4 = j.skip_hi4 = -1;
   SlabRanges& r = j.r;

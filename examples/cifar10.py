@@ -34,8 +34,9 @@ from torch_distlearn_amd import LocalhostTree  # noqa: E402
 from torch_distlearn_amd.checkpoint import results_dir, resume_trainer, save_trainer  # noqa: E402
 from torch_distlearn_amd.data import Dataset, DeviceLoader  # noqa: E402
 from torch_distlearn_amd.engine import DataParallelTrainer  # noqa: E402
-from torch_distlearn_amd.launch import (add_checkpoint_flags, add_node_flags, device_of, node_opts,  # noqa: E402
-                                        quiet_unless_root)
+from torch_distlearn_amd.launch import (add_checkpoint_flags, add_node_flags, add_schedule_flags,  # noqa: E402
+                                        device_of, node_opts, quiet_unless_root)
+from torch_distlearn_amd import schedules  # noqa: E402
 from torch_distlearn_amd.models import CifarConvNet  # noqa: E402
 from torch_distlearn_amd.utils.metrics import ConfusionMatrix, JsonlMetrics  # noqa: E402
 
@@ -54,6 +55,7 @@ def main():
     ap.add_argument("--unroll", type=int, default=16, help="steps per replayed hipGraph (HIP fast path)")
     ap.add_argument("--metrics", default=None, help="JSON-lines metrics file (node 1)")
     add_checkpoint_flags(ap)
+    add_schedule_flags(ap)
     opt = ap.parse_args()
     node_opts(opt)
     dev = device_of(opt)
@@ -78,7 +80,8 @@ def main():
     torch.manual_seed(0)  # same init on all nodes (cifar10.lua:105)
     model = CifarConvNet(seed=0).to(dev)
     trainer = DataParallelTrainer(model, tree, lr=opt.learningRate, backend=backend, compute_dtype=dt,
-                                  graph=graph, max_batch=per_node)
+                                  graph=graph, max_batch=per_node,
+                                  lr_schedule=schedules.from_options(opt, opt.learningRate))
     first = 1
     if opt.resume:
         st = resume_trainer(results_dir(opt.save, opt.resultsRoot), trainer)
@@ -116,6 +119,7 @@ def main():
         print(f"Epoch {epoch}: train loss {float(loss):.4f}  {nb * per_node * opt.numNodes / dt_s:.0f} img/s "
               f"({nb} steps of {per_node} per node; {path})")
         print(conf)
+        print(f"Epoch {epoch}: learning rate {trainer.lr:.8g} (last of {nb} steps; --lrSchedule {opt.lrSchedule})")
         trainer.synchronize()  # cifar10.lua:208
         conf.zero()
         ntb = test_b.numBatches() if not opt.maxSteps else min(opt.maxSteps, test_b.numBatches())

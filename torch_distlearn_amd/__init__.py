@@ -15,10 +15,11 @@ from .parallel import (AllReduceEA, AllReduceSGD, AsyncEA, Communicator, FlatBuf
 from .ops.flat import FlatParams
 from .utils.color_print import printClient, printServer
 from .utils.walk import walkTable, walk_table
-from . import _native
+from . import _native, schedules
+from .schedules import constant, cosine, step_decay
 
 __version__ = "0.1.0"
 
 __all__ = ["AllReduceSGD", "AllReduceEA", "AsyncEA", "Tree", "LocalhostTree", "Communicator", "FlatBuffer",
            "FlatParams", "GradBucketer", "init_communicator", "printServer", "printClient", "walkTable",
-           "walk_table"]
+           "walk_table", "schedules", "constant", "step_decay", "cosine"]

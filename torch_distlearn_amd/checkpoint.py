@@ -11,7 +11,8 @@ block commented out, examples/EASGD_server.lua:37-48) but never writes
   with ``torch.load(..., weights_only=True)``.
 * ``optState`` -- ``torch.save`` of a dict of tensors/numbers: step counters,
   ``stepsPerNode`` (AllReduceSGD), ``center`` (AllReduceEA / AsyncEA), the
-  momentum buffer, learning rate, epoch and the BatchNorm running statistics.
+  momentum buffer, learning rate, ``sched_step`` (the position in the trainer's
+  ``lr_schedule=``), epoch and the BatchNorm running statistics.
 * ``Log.txt`` / ``ErrorRate.log`` -- text logs (:class:`~torch_distlearn_amd.utils.metrics.Logger`).
 
 Training resume (SURVEY §5.4 "resume = load + synchronizeParameters"):
@@ -104,7 +105,9 @@ def trainer_state(trainer) -> Dict[str, Any]:
 
 def _trainer_state(trainer) -> Dict[str, Any]:
     """Collect the algorithm state of a DataParallelTrainer for ``optState``."""
-    st: Dict[str, Any] = {"lr": trainer.lr, "steps": trainer.steps}
+    st: Dict[str, Any] = {"lr": trainer.lr, "steps": trainer.steps,
+                          # position in the learning-rate schedule (engine lr_schedule=; 0 without one)
+                          "sched_step": int(getattr(trainer, "sched_step", 0))}
     if trainer.sgd is not None:
         st["stepsPerNode"] = trainer.sgd.stepsPerNode
     if trainer.ea is not None:
@@ -119,6 +122,7 @@ def restore_trainer_state(trainer, st: Dict[str, Any]) -> None:
     """Inverse of :func:`trainer_state` (node-local parts)."""
     trainer.steps = int(st.get("steps", 0))
     trainer.lr = float(st.get("lr", trainer.lr))
+    trainer.sched_step = int(st.get("sched_step", 0))  # a state from before schedules: the start
     if trainer.sgd is not None and "stepsPerNode" in st:
         trainer.sgd.stepsPerNode.copy_(st["stepsPerNode"])
     if trainer.ea is not None and "center" in st:

@@ -23,7 +23,13 @@ way to drive them:
 * the update is ONE fused kernel (1/n + SGD + bf16 shadow refresh);
 * ``graph=True`` captures forward + backward + all-reduce + update into one
   hipGraph and replays it (RCCL collectives are capturable), removing the
-  per-kernel host launch cost that dominates a 4-layer convnet step.
+  per-kernel host launch cost that dominates a 4-layer convnet step;
+* ``lr_schedule=`` (:mod:`torch_distlearn_amd.schedules`): the learning rate
+  follows a host-side schedule in every mode.  A kernel argument is frozen
+  when a step is captured, so the captured update kernels read the rate from
+  a small device ring instead (step ``i`` of a graph reads ``ring[i]``) and
+  the trainer writes the next rates into it with one small launch before
+  every replay.
 """
 from __future__ import annotations
 
@@ -34,12 +40,15 @@ from typing import Any, Callable, Optional
 
 import torch
 
-from .ops.flat import FlatParams, fill_
+from .ops.flat import FlatParams, fill_, lr_ring_set_
 from .parallel.allreduce_ea import AllReduceEA
 from .parallel.allreduce_sgd import AllReduceSGD
 from .parallel.buckets import GradBucketer
 from .parallel.comm import runs_collectives
 from .parallel.tree import Tree
+from .schedules import as_fp32, constant
+
+LR_RING = 64  # floats in the device ring of learning rates: the longest graph a schedule can feed
 
 
 def agree_on_policy(comm, local_ms: dict) -> tuple:
@@ -107,7 +116,8 @@ class DataParallelTrainer:
                  backend: str = "torch", compute_dtype: torch.dtype = torch.bfloat16,
                  bucket_bytes: int = 4 << 20, overlap: bool = True, graph: bool = False,
                  loss_fn: Optional[Callable] = None, max_batch: Optional[int] = None,
-                 async_ea: Optional[Any] = None, grad_comm_dtype: str = "fp32"):
+                 async_ea: Optional[Any] = None, grad_comm_dtype: str = "fp32",
+                 lr_schedule: Optional[Callable[[int], float]] = None):
         self.model = model
         self.tree = tree
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
@@ -116,6 +126,18 @@ class DataParallelTrainer:
         self.compute_dtype = compute_dtype
         dev = next(model.parameters()).device
         self.device = dev
+        # lr_schedule: t -> rate of update t (schedules.py); sched_step = updates
+        # applied so far.  Eager steps set self.lr from it before the step body;
+        # captured steps read the rate from the device ring (allocated once:
+        # policy changes that drop graphs do not move it), _advance_lr.
+        self.lr_schedule = lr_schedule
+        self.sched_step = 0
+        self._cap_slot: Optional[int] = None  # ring slot of the step body being captured
+        self._lr_ring = None
+        if lr_schedule is not None:
+            self.lr = self._rate(0)
+            if dev.type == "cuda":
+                self._lr_ring = torch.full((LR_RING,), self.lr, dtype=torch.float32, device=dev)
         bf16_shadow = dev.type == "cuda" and compute_dtype == torch.bfloat16
         self.flat = FlatParams(model, grads=True, shadow_bf16=bf16_shadow)
         self.mom = self.flat.like(0.0) if momentum else None
@@ -171,7 +193,7 @@ class DataParallelTrainer:
         if (algo == "sgd" and getattr(self.executor, "bucket_updates_safe", False)
                 and os.environ.get("DISTLEARN_BUCKET_UPDATE", "0") == "1"):
             self.bucket_updates = self.sgd.enable_bucket_updates(
-                self.flat, lambda: self.lr, momentum=momentum, weight_decay=weight_decay, momentum_buf=self.mom)
+                self.flat, self._lr_arg, momentum=momentum, weight_decay=weight_decay, momentum_buf=self.mom)
         # Whether the gradients go through a collective: AllReduceSGD at N > 1
         # (or at world 1 with the collectives forced through RCCL -- the
         # multi-node configuration rehearsed on one GPU, bench.py --nworld-path).
@@ -217,6 +239,73 @@ class DataParallelTrainer:
         # examples' every-sample training confusion matrix (one GPU kernel)
         self.step_hooks: list = []
 
+    # ------------------------------------------------------------------ learning rate
+    def _rate(self, t: int) -> float:
+        """The schedule's value for update ``t``, rounded to fp32 once: the
+        one value the eager kernel argument, the ring and ``lr`` all carry."""
+        return as_fp32(self.lr_schedule(int(t)))
+
+    def _lr_arg(self):
+        """The rate the update of the step body being run takes: the host
+        float, or -- a body captured under a schedule -- its ring slot (a
+        1-element view the kernels read on the device at replay time)."""
+        if self._cap_slot is not None and self._lr_ring is not None:
+            return self._lr_ring[self._cap_slot:self._cap_slot + 1]
+        return self.lr
+
+    @contextlib.contextmanager
+    def _ring_slot(self, i: int):
+        """Capture a step body whose update reads ``ring[i]`` (no schedule:
+        the host float, as ever)."""
+        prev, self._cap_slot = self._cap_slot, (i if self._lr_ring is not None else None)
+        try:
+            yield
+        finally:
+            self._cap_slot = prev
+
+    def _advance_lr(self, k: int = 1, ring: bool = False, advance: bool = True) -> None:
+        """Schedule mode, before ``k`` updates run: ``ring`` -- the next ``k``
+        rates go into the device ring on the current stream, right before the
+        replay that reads them; ``advance`` -- count the updates and leave
+        ``lr`` at the last rate used (a trial replay whose state is restored
+        feeds the ring without counting)."""
+        if self.lr_schedule is None:
+            return
+        vals = [self._rate(self.sched_step + i) for i in range(k)]
+        if ring and self._lr_ring is not None:
+            lr_ring_set_(self._lr_ring, 0, vals)
+        if advance:
+            self.sched_step += k
+            self.lr = vals[-1]
+
+    def set_lr(self, value: float) -> None:
+        """Change the learning rate from now on.  With ``lr_schedule=`` the
+        schedule becomes the constant ``value``.  Without one the rate is a
+        kernel argument frozen into every captured hipGraph, so this raises
+        once graphs exist (plain ``trainer.lr = v`` keeps its old meaning:
+        it reaches eager steps and later captures only)."""
+        if self.lr_schedule is not None:
+            self.lr_schedule = constant(value)
+            self.lr = as_fp32(value)
+            return
+        if self._graph is not None or self._multi:
+            raise RuntimeError("set_lr: the captured hipGraphs hold the learning rate they were captured with; "
+                               "construct the trainer with lr_schedule= (torch_distlearn_amd.schedules) to change "
+                               "the rate of a graph run")
+        self.lr = value
+
+    def _agree_sched_step(self) -> None:
+        """After a parameter synchronisation every node holds the winner's
+        parameters (the node with the most steps): it takes the winner's
+        place in the schedule too, or uneven epochs would leave the nodes on
+        different rates for ever after.  One max on the control plane.  Not
+        for AsyncEA (the server never joins; each client follows its own count)."""
+        if self.lr_schedule is None or self.algo not in ("sgd", "ea") or self.tree.numNodes <= 1:
+            return
+        t = torch.tensor([self.sched_step], dtype=torch.int64)
+        self.tree.comm.all_reduce_host(t, "max")
+        self.sched_step = int(t[0])
+
     # ------------------------------------------------------------------
     def _forward_backward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         if self.executor is not None:
@@ -258,7 +347,7 @@ class DataParallelTrainer:
             armed = bool(arm(x)) if arm is not None else False
         try:
             if self.algo == "sgd":
-                self.sgd.step(f, self.lr, momentum=self.momentum, weight_decay=self.weight_decay,
+                self.sgd.step(f, self._lr_arg(), momentum=self.momentum, weight_decay=self.weight_decay,
                               momentum_buf=self.mom, slabs=self._slabs, skip=self._side)
             elif self.algo == "ea" or (self.algo == "async" and local):
                 self._local_update()
@@ -282,7 +371,7 @@ class DataParallelTrainer:
     def _local_update(self) -> None:
         from .ops.flat import flat_sgd_
 
-        flat_sgd_(self.flat, self.lr, slot=None, mom=self.mom, momentum=self.momentum,
+        flat_sgd_(self.flat, self._lr_arg(), slot=None, mom=self.mom, momentum=self.momentum,
                   weight_decay=self.weight_decay, slabs=self._slabs, skip=self._side)
 
     def step(self, x, y: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -305,6 +394,7 @@ class DataParallelTrainer:
         # step's body (run() replays the local steps as unrolled graphs).
         local = self.aea is not None and (self.aea.step + 1) % self.aea.tau != 0
         if not self.graph:
+            self._advance_lr()
             loss = self._step_body(x, y, local=local)
         else:
             if self._graph is None:
@@ -316,6 +406,9 @@ class DataParallelTrainer:
                     self._static[1].copy_(y, non_blocking=True)
             elif self._static[0] is not dev_loader:
                 raise ValueError("the captured step is bound to another DeviceLoader")
+            # (an AsyncEA client's graph holds no update: its eager _local_update
+            # below takes the host float this leaves in self.lr)
+            self._advance_lr(ring=True)
             self._replay(self._graph)
             self._track()
             if self.sgd is not None:
@@ -390,6 +483,7 @@ class DataParallelTrainer:
                 k = max((u for u in self._multi if isinstance(u, int) and u <= cap), default=1) if fast else 1
             if k > 1 or (key is not None and k >= 1):
                 g, loss = self._multi[key if key is not None else k]
+                self._advance_lr(k, ring=True)
                 self._replay(g)
                 if self.ea is not None:
                     self.ea.step += k  # the graph ran k local steps (+ the round when key is set)
@@ -447,8 +541,11 @@ class DataParallelTrainer:
             self._capture_multi(loader, k)
         if new:
             saved = self._snapshot(loader)
+            # (trial replays: valid rates in the ring, the schedule's position untouched)
+            self._advance_lr(ring=True, advance=False)
             self._replay(self._graph)
             for k in new:
+                self._advance_lr(k[1] if isinstance(k, tuple) else k, ring=True, advance=False)
                 self._replay(self._multi[k][0])
             self._restore(saved, loader)
             torch.cuda.current_stream().synchronize()
@@ -558,7 +655,7 @@ class DataParallelTrainer:
                 or self.algo == "async"  # a syncing step's update must follow the elastic move
                 or not callable(getattr(ex, "side_update", None))):
             return
-        rng = ex.side_update(lambda: self.lr, self.momentum, self.weight_decay, self.mom,
+        rng = ex.side_update(self._lr_arg, self.momentum, self.weight_decay, self.mom,
                              self.flat.slot if self.algo == "sgd" else None)
         self._side = rng
 
@@ -582,6 +679,7 @@ class DataParallelTrainer:
         saved = self._snapshot(loader)
         self._capture(loader, None)
         g = self._graph
+        self._advance_lr(ring=True, advance=False)  # every replay below reads the same valid rate
         self._replay(g)
         torch.cuda.synchronize()
         self.tree.comm.barrier()
@@ -654,11 +752,15 @@ class DataParallelTrainer:
         self.captures += 1
         ea_round = isinstance(k, tuple) and k[0] == "ea"
         n = k[1] if isinstance(k, tuple) else k
+        if self.lr_schedule is not None and n > LR_RING:
+            raise ValueError(f"lr_schedule: a captured graph of {n} steps does not fit the device ring of "
+                             f"{LR_RING} learning rates (tau above {LR_RING}: use a smaller tau or graph=False)")
         local = self.aea is not None
         g = torch.cuda.CUDAGraph()
         with _capturing(self.tree.comm), self._seq_record(g), torch.cuda.graph(g, capture_error_mode=_CAPTURE_MODE):
             for j in range(n):
-                loss = self._step_body(loader, None, prep_next=j + 1 < n, local=local)
+                with self._ring_slot(j):
+                    loss = self._step_body(loader, None, prep_next=j + 1 < n, local=local)
             if ea_round:
                 self.ea.elastic_round()
         if self.sgd is not None:
@@ -709,12 +811,13 @@ class DataParallelTrainer:
         bk.start_capture_profile()
         try:
             with _capturing(self.tree.comm), self._seq_record(g), \
-                    torch.cuda.graph(g, capture_error_mode=_CAPTURE_MODE):
+                    torch.cuda.graph(g, capture_error_mode=_CAPTURE_MODE), self._ring_slot(0):
                 self._step_body(loader, None)
         finally:
             recs = bk.stop_capture_profile()
         self.sgd.stepsPerNode[self.tree.nodeIndex - 1] -= 1  # the capture counted a step (not executed)
         runs = []
+        self._advance_lr(ring=True, advance=False)  # the replays read a valid rate; the schedule stays put
         try:
             for i in range(steps + 1):  # the first replay is a warm-up
                 self._replay(g)
@@ -773,7 +876,8 @@ class DataParallelTrainer:
         torch.cuda.current_stream().wait_stream(s)
         self._restore(saved, x)
         g = torch.cuda.CUDAGraph()
-        with _capturing(self.tree.comm), self._seq_record(g), torch.cuda.graph(g, capture_error_mode=_CAPTURE_MODE):
+        with _capturing(self.tree.comm), self._seq_record(g), torch.cuda.graph(g, capture_error_mode=_CAPTURE_MODE), \
+                self._ring_slot(0):
             loss = self._step_body(sx, sy)
         if self.sgd is not None:
             # the warm-up + capture bodies counted steps; undo (replay() counts itself)
@@ -789,6 +893,7 @@ class DataParallelTrainer:
             self.sgd.synchronizeParameters(self.flat)
         elif self.algo == "ea":
             self.ea.synchronizeCenter(self.flat)
+        self._agree_sched_step()
 
     def synchronize_parameters(self) -> None:
         """Initial synchronisation (AsyncEA: receive the server's center,
@@ -799,6 +904,7 @@ class DataParallelTrainer:
             self.ea.synchronizeParameters(self.flat)
         else:
             self.aea.initClient(self.flat)
+        self._agree_sched_step()
 
     def finish(self) -> None:
         """AsyncEA client: tell the server this client is done."""

@@ -62,6 +62,18 @@ def add_checkpoint_flags(ap: argparse.ArgumentParser) -> argparse.ArgumentParser
     return ap
 
 
+def add_schedule_flags(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
+    """Learning-rate schedule flags (schedules.from_options turns them into
+    the trainer's ``lr_schedule=``).  The defaults are today's constant
+    ``--learningRate``.  Steps count updates from the start of training."""
+    ap.add_argument("--lrSchedule", default="constant", choices=["constant", "step", "cosine"])
+    ap.add_argument("--lrDecay", type=float, default=0.1, help="step: factor applied at every milestone")
+    ap.add_argument("--lrMilestones", default="", help="step: comma-separated update counts, e.g. 8000,16000")
+    ap.add_argument("--warmupSteps", type=int, default=0, help="linear warm-up from 0 over this many updates")
+    ap.add_argument("--totalSteps", type=int, default=0, help="cosine: updates until the rate reaches 0")
+    return ap
+
+
 def node_opts(opt) -> None:
     """Fill nodeIndex/numNodes/gpu from torchrun-style env when not given;
     export ``--commTimeout`` for the communicators."""

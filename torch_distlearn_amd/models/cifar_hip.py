@@ -35,7 +35,7 @@ from typing import List, Optional
 import torch
 
 from .._native import native, stream_handle
-from ..ops.flat import HEADER
+from ..ops.flat import HEADER, _lr_args
 from ..parallel.comm import runs_collectives
 from .cifar_convnet import BN_EPS, BN_MOMENTUM, KSIZE, CifarConvNet
 
@@ -774,8 +774,9 @@ class CifarHIPExecutor:
         p, g, mom, p16, slot = sd["args"]
         mo, wd = sd["mw"]
         lo, hi = job["range"]
-        self.C.set_conv_side_sgd(p, g, mom, p16, slot, float(sd["lr"]()), mo, wd, lo, hi, *job["slabs"],
-                                 0)  # 0: one float4 per thread over the range
+        lr, lr_dev = _lr_args(sd["lr"](), True)  # a tensor rate: the side job reads it on the device
+        self.C.set_conv_side_sgd(p, g, mom, p16, slot, lr, mo, wd, lo, hi, *job["slabs"],
+                                 0, lr_dev)  # 0: one float4 per thread over the range
 
     def defer_slab_reduce(self):
         """Leave every split-K weight gradient in its slabs: the slab_reduce

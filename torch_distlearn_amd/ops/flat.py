@@ -176,10 +176,28 @@ def _scale_from_slot(slot):
     return 1.0 / n if n > 1 else 1.0
 
 
-def sgd_update_(p: torch.Tensor, g: torch.Tensor, lr: float, slot: torch.Tensor | None = None,
+def _lr_args(lr, cuda: bool):
+    """(immediate rate, lr_dev pointer) for the native update kernels.  ``lr``
+    is a float, or a 1-element fp32 tensor: on the GPU its pointer goes to the
+    kernels (they read the rate from memory: a captured launch follows a
+    schedule), on the CPU it is read with ``float()``."""
+    if not isinstance(lr, torch.Tensor):
+        return float(lr), 0
+    if lr.numel() != 1 or lr.dtype != torch.float32:
+        raise ValueError("sgd_update_: a tensor learning rate is one fp32 element")
+    if not cuda:
+        return float(lr), 0
+    if not lr.is_cuda:
+        raise ValueError("sgd_update_: a tensor learning rate for GPU parameters must be on the GPU")
+    return 0.0, lr.data_ptr()
+
+
+def sgd_update_(p: torch.Tensor, g: torch.Tensor, lr, slot: torch.Tensor | None = None,
                 mom: torch.Tensor | None = None, momentum: float = 0.0, weight_decay: float = 0.0,
                 shadow: torch.Tensor | None = None, slabs=None, tail=None, skip=None) -> None:
     """p -= lr * (g/n + wd*p) [with momentum buffer]; n from ``slot`` (device).
+    ``lr``: a float, or a 1-element fp32 CUDA tensor the kernel reads the rate
+    from (bitwise the same update as that fp32 value passed as a float).
     ``g`` is fp32, or bf16 (the all-reduced wire copy of grad_comm_dtype="bf16").
     ``slabs``: [(offset into p, numel, slab tensor [splits * numel], splits)]:
     in those ranges the gradient is the sum of the split-K slabs instead of
@@ -190,6 +208,7 @@ def sgd_update_(p: torch.Tensor, g: torch.Tensor, lr: float, slot: torch.Tensor 
     (updated inside the step by a conv launch's side job)."""
     # an armed next-step preparation (executor arm_next_prep) rides the slab-capable launch
     armed = p.is_cuda and native().sgd_next_prep_armed()
+    lr, lr_dev = _lr_args(lr, p.is_cuda)
     if slabs or tail is not None or skip is not None or armed:
         if not p.is_cuda or g.dtype != torch.float32:
             raise ValueError("sgd_update_: slab gradients / the next-step preparation need an fp32 gradient "
@@ -199,16 +218,17 @@ def sgd_update_(p: torch.Tensor, g: torch.Tensor, lr: float, slot: torch.Tensor 
         if tail is not None:
             o, n, t, k, cout, taps, cp, c = tail
             tl, tptr = [int(o), int(n), int(k), int(cout), int(taps), int(cp), int(c)], t.data_ptr()
-        native().sgd_update_slabs(p.data_ptr(), g.data_ptr(), _ptr(mom), _ptr(shadow), _ptr(slot), float(lr),
+        native().sgd_update_slabs(p.data_ptr(), g.data_ptr(), _ptr(mom), _ptr(shadow), _ptr(slot), lr,
                                   float(momentum), float(weight_decay), p.numel(), [int(o) for o, _, _, _ in slabs],
                                   [int(n) for _, n, _, _ in slabs], [t.data_ptr() for _, _, t, _ in slabs],
                                   [int(k) for _, _, _, k in slabs], tl, tptr,
-                                  int(skip[0]) if skip else 0, int(skip[1]) if skip else 0, stream_handle())
+                                  int(skip[0]) if skip else 0, int(skip[1]) if skip else 0, stream_handle(),
+                                  lr_dev)
         return
     if p.is_cuda:
         fn = native().sgd_update_g16 if g.dtype == torch.bfloat16 else native().sgd_update
-        fn(p.data_ptr(), g.data_ptr(), _ptr(mom), _ptr(shadow), _ptr(slot), float(lr), float(momentum),
-           float(weight_decay), p.numel(), stream_handle())
+        fn(p.data_ptr(), g.data_ptr(), _ptr(mom), _ptr(shadow), _ptr(slot), lr, float(momentum),
+           float(weight_decay), p.numel(), stream_handle(), lr_dev)
         return
     with torch.no_grad():
         d = g.float() * _scale_from_slot(slot)
@@ -229,12 +249,13 @@ def _overlaps(x: torch.Tensor, y: torch.Tensor) -> bool:
     return xs < ys + y.numel() * y.element_size() and ys < xs + x.numel() * x.element_size()
 
 
-def flat_sgd_(flat: "FlatParams", lr: float, slot: torch.Tensor | None = None, mom: torch.Tensor | None = None,
+def flat_sgd_(flat: "FlatParams", lr, slot: torch.Tensor | None = None, mom: torch.Tensor | None = None,
               momentum: float = 0.0, weight_decay: float = 0.0, grad: torch.Tensor | None = None,
               slabs=None, skip=None) -> None:
     """The fused update over a FlatParams' parameter body: the 64-element
     header (whose gradient element is the participation count) is left out,
-    so ``n`` never flows into the parameter buffer.  ``grad``: the gradient
+    so ``n`` never flows into the parameter buffer.  ``lr``: a float or a
+    1-element fp32 tensor (:func:`sgd_update_`).  ``grad``: the gradient
     buffer to read (default ``flat.grad``; ``flat.grad16`` for bf16 comm).
     ``slabs``: [(leaf index, slab tensor, splits, Cout, taps, Cp, C)] whose
     gradient is still in split-K slabs [splits][Cout][taps][Cp] (see
@@ -262,6 +283,22 @@ def flat_sgd_(flat: "FlatParams", lr: float, slot: torch.Tensor | None = None, m
                 momentum=momentum, weight_decay=weight_decay,
                 shadow=None if flat.shadow is None else flat.shadow[H:], slabs=rng, tail=tail,
                 skip=None if skip is None else (max(0, skip[0] - H), skip[1] - H))
+
+
+def lr_ring_set_(ring: torch.Tensor, offset: int, values) -> None:
+    """ring[offset : offset + len(values)] = values (fp32) on the current
+    stream: the values travel as kernel arguments, 32 per launch, so no host
+    staging buffer has to stay alive until the device gets there."""
+    vals = [float(v) for v in values]
+    if ring.dtype != torch.float32 or not ring.is_contiguous():
+        raise ValueError("lr_ring_set_: a contiguous fp32 ring")
+    if offset < 0 or offset + len(vals) > ring.numel():
+        raise ValueError("lr_ring_set_: values outside the ring")
+    if not ring.is_cuda:
+        ring[offset:offset + len(vals)] = torch.tensor(vals, dtype=torch.float32)
+        return
+    for i in range(0, len(vals), 32):
+        native().lr_ring_set(ring.data_ptr(), ring.numel(), offset + i, vals[i:i + 32], stream_handle())
 
 
 def scale_by_count_(x: torch.Tensor, slot: torch.Tensor) -> None:

@@ -103,13 +103,15 @@ class AllReduceSGD:
         self._remember(grads)
         self._count_step()
 
-    def step(self, flat: FlatParams, lr: float, momentum: float = 0.0, weight_decay: float = 0.0,
+    def step(self, flat: FlatParams, lr, momentum: float = 0.0, weight_decay: float = 0.0,
              momentum_buf: Optional[torch.Tensor] = None, already_reduced: bool = False, slabs=None,
              skip=None) -> None:
         """Fused ``sumAndNormalizeGradients`` + SGD update over a FlatParams:
         all-reduce (unless the bucketer already did), then ONE kernel
         ``p -= lr*(g/n + wd*p)`` (+momentum, + bf16 shadow refresh).  This is
-        examples/cifar10.lua:184-191 in one launch.  ``slabs`` (one node
+        examples/cifar10.lua:184-191 in one launch.  ``lr``: a float, or a
+        1-element fp32 CUDA tensor the kernel reads the rate from (passed
+        straight through to ops/flat.py flat_sgd_).  ``slabs`` (one node
         only: nothing is all-reduced): leaves whose gradient the update sums
         from split-K slabs itself (ops/flat.py flat_sgd_); ``skip``: a flat
         element range [lo, hi) already updated inside the step (a conv
@@ -136,7 +138,8 @@ class AllReduceSGD:
                               momentum_buf: Optional[torch.Tensor] = None) -> bool:
         """Fold the fused SGD of :meth:`step` into the bucketer: each bucket's
         parameters are updated on the comm stream right after its all-reduce
-        (buckets.py set_early_update).  ``lr_fn()`` returns the current rate.
+        (buckets.py set_early_update).  ``lr_fn()`` returns the current rate
+        (a float or a 1-element fp32 CUDA tensor, as :meth:`step`'s ``lr``).
         Only for callers whose backward never reads a parameter after its
         bucket is complete (the HIP executors).  Returns whether it is on."""
         bk = self.bucketer
