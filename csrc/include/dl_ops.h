@@ -96,6 +96,25 @@ void gather_normalize(uintptr_t images, uintptr_t idx, uintptr_t out, int B, int
 
 // conv_igemm.hip --------------------------------------------------------------
 // NHWC activations, KRSC weights, stride 1, same padding, Cin power of two >= 8.
+//
+// The `tile` argument of every conv_fwd* entry point (and of conv_region_ok,
+// conv_fix_ok, conv_fwd_stat_rows) is a packed word (Python: ops/conv.py
+// pack_tile).  Its per-call values hold for that call only and never write
+// the process-wide set_conv_* settings:
+//   bits 0-3   tile id: 0 = 128x128, 1 = 64x64, 2 = 128x64 (BM x BN)
+//   bits 4-7   LDS ring stages of the streaming kernel, 2..4 (0 = set_conv_stages).
+//              The ResNet-50 1x1 GEMMs pick 2 (96 -> 64 KiB of LDS: two
+//              workgroups per CU, which the short-K GEMMs need --
+//              scripts/bench_gemm1x1.py SWEEP=1, ops/conv.py _plan_1x1), as do
+//              the dgrads of a step that overlaps its all-reduce.
+//   bits 8-11  waves per workgroup of the streaming kernel, 4 or 8 (0 = set_conv_waves)
+//   bit 16     whole-image region tiles allowed, as under set_conv_region(2)
+//              (set_conv_region(0) still forces the streaming kernel)
+//   bit 20     keep the split-K slabs: no combine launch, the consumer sums them
+//              (bn_pool.hip combine_bwd_reduce, the head's softmax)
+//   bit 24     pair-packed first-layer weights over the 4-channel input
+//              (conv_fwd's first-layer kernel and conv_wgrad; dl_common.h pack1_index)
+// conv_wgrad's tile is 1 = 64x64 or 2 = 128x128 (Cout x K) plus bit 24.
 int conv_fwd(uintptr_t x, uintptr_t w, uintptr_t y, uintptr_t stats, uintptr_t slab, int B, int H, int W, int Cin,
              int Cout, int KS, int tile, int splits, uintptr_t stream);
 int conv_fwd_stat_rows(int B, int H, int W, int Cin, int Cout, int KS, int tile, int splits);
@@ -111,8 +130,6 @@ void set_conv_fwd_pf(int on);
 void set_head_stamps(uintptr_t buf);
 void set_bn_stamps(uintptr_t buf);
 void set_conv_wgrad_stamps(uintptr_t buf);
-// the next conv_fwd (region kernel, forward with statistics) pools its input on load
-// from the previous block's pre-BN output (BN coefficients from its accumulated sums)
 int conv_region_ok(int B, int H, int W, int Cin, int Cout, int KS, int tile, int splits = 1);
 int conv_fwd_fix(uintptr_t x, uintptr_t w, uintptr_t y, uintptr_t stats, uintptr_t slab, int B, int H, int W, int Cin,
                  int Cout, int KS, int tile, int splits, uintptr_t y_prev, uintptr_t coef, uintptr_t rows,
@@ -126,10 +143,6 @@ int conv_fwd_ex(uintptr_t x, uintptr_t w, uintptr_t y, uintptr_t stats, uintptr_
 void conv_wgrad_ex(uintptr_t dy, uintptr_t x, uintptr_t out, int B, int Ho, int Wo, int Hp, int Wp, int dHp, int dWp,
                    int dpad, int Cin, int Cout, int KH, int KW, int S, int splits, int ldo, int tile,
                    uintptr_t stream);
-// first-layer weight gradient from an LDS-resident input region (Cin 8, Cout 64):
-// fp32 slabs [B * H / R][64][ldo]; returns the split count
-// position-major wgrad plan at `steps` K steps per workgroup: {max splits a
-// column tile needs, workgroups with work} ({0, 0}: B does not take it)
 void conv_wgrad(uintptr_t dy, uintptr_t x, uintptr_t out, int B, int H, int W, int Cin, int Cout, int KS, int splits,
                 int ldo, int tile, int atomic_creal, uintptr_t stream);
 void set_reduce_atomic_conv(int rows);

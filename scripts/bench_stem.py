@@ -43,8 +43,7 @@ def main():
     y = torch.empty(N, Ho, Wo, cout, dtype=torch.bfloat16, device=dev)
     out = {"s2d_input_us": round(timeit(lambda: C.s2d_stem_input(x.data_ptr(), S.data_ptr(), N, H, H, Hs, Ws, 3, s)), 1)}
     for name, tile in (("t2_w8", 2 | (3 << 4) | (8 << 8)), ("t2", 2), ("t2_w4", 2 | (3 << 4) | (4 << 8)),
-                       ("t1", 1), ("t2_again", 2), ("t2_w8_again", 2 | (3 << 4) | (8 << 8)),
-                       ("t2_sw", 2 | (1 << 21)), ("t2_w8_sw", 2 | (3 << 4) | (8 << 8) | (1 << 21))):
+                       ("t1", 1), ("t2_again", 2), ("t2_w8_again", 2 | (3 << 4) | (8 << 8))):
         out["s2d16_" + name] = round(timeit(lambda: C.conv_fwd_ex(S.data_ptr(), w4.data_ptr(), y.data_ptr(), 0, 0, N, Ho,
                                                                    Wo, Hs, Ws, 16, cout, 4, 4, 1, 0, 0, 0, 0, 0, 0,
                                                                    tile, 1, s)), 1)

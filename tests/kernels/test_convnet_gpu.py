@@ -1059,3 +1059,113 @@ def test_executor_in_launch_combine(C, monkeypatch, B, atomic):
     else:
         noise = max(rel(grads[i], grads[j]) for i, j in ((1, 2), (1, 3), (2, 3)))
         assert min(rel(grads[i], grads[0]) for i in (1, 2, 3)) < max(3 * noise, 6e-2)
+
+
+# --------------------------------------------------------------------------- per-call options of the tile word
+def _conv5(C, x, w, tile, B, H, cin, cout, stats=True):
+    """conv_fwd (5x5, unsplit) of the padded NHWC x -> (y, statistics rows or None)."""
+    dev = x.device
+    y = torch.empty(B, H, H, cout, dtype=torch.bfloat16, device=dev)
+    rows = C.conv_fwd_stat_rows(B, H, H, cin, cout, 5, tile, 1)
+    st = torch.full((rows, 2, cout), float("nan"), device=dev) if stats else None
+    T = C.conv_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), st.data_ptr() if stats else 0, 0, B, H, H, cin, cout, 5,
+                   tile, 1, _s())
+    torch.cuda.synchronize()
+    assert T == rows
+    return y, st
+
+
+def _conv5_operands(B, H, cin, cout, seed):
+    dev = torch.device("cuda")
+    g = torch.Generator(device=dev).manual_seed(seed)
+    x = torch.randn(B, H, H, cin, device=dev, generator=g).to(torch.bfloat16)
+    w = (torch.randn(cout, 5, 5, cin, device=dev, generator=g) * 0.05).to(torch.bfloat16)
+    return x, w
+
+
+@pytest.mark.parametrize("B", [4, 3])
+def test_conv_fwd_region_images_bit(C, B):
+    """The tile word's region_images bit selects the whole-image region tiles
+    for one call exactly as set_conv_region(2) does for the process: bitwise
+    equal output and statistics rows (8x8 images: two per 128-row tile; B = 3
+    leaves an M tail), both within test_conv_fwd_and_stats' bound of fp32."""
+    from torch_distlearn_amd.ops.conv import pack_tile
+
+    H, cin, cout = 8, 64, 64
+    x, w = _conv5_operands(B, H, cin, cout, 31 + B)
+    ref = F.conv2d(x.float().permute(0, 3, 1, 2), w.float().permute(0, 3, 1, 2), padding=2).permute(0, 2, 3, 1)
+    xp = _pad(x)
+    bit = pack_tile(2, region_images=True)
+    assert C.conv_region_ok(B, H, H, cin, cout, 5, bit, 1) == 1
+    assert C.conv_region_ok(B, H, H, cin, cout, 5, 2, 1) == 0
+    C.set_conv_region(2)
+    try:
+        y_mode, st_mode = _conv5(C, xp, w, 2, B, H, cin, cout)
+    finally:
+        C.set_conv_region(1)
+    y_bit, st_bit = _conv5(C, xp, w, bit, B, H, cin, cout)
+    assert torch.equal(y_mode, y_bit)
+    assert torch.equal(st_mode, st_bit)
+    assert _rel(y_mode, ref) < 8e-3
+    assert _rel(y_bit, ref) < 8e-3
+
+
+def test_conv_fwd_per_call_options_leave_process_settings(C):
+    """Per-call stages / region_images hold for their call only: the calls
+    after them run under the unchanged process settings."""
+    from torch_distlearn_amd.ops.conv import pack_tile
+
+    B, H, cin, cout = 4, 8, 128, 64
+    x, w = _conv5_operands(B, H, cin, cout, 41)
+    xp = _pad(x)
+    region_ok = lambda h, tile: C.conv_region_ok(B, h, h, cin, cout, 5, tile, 1)  # noqa: E731
+    C.set_conv_region(0)
+    try:
+        # the K order does not depend on the ring depth: bitwise equal at any stage count
+        y_st2, s_st2 = _conv5(C, xp, w, pack_tile(2, stages=2), B, H, cin, cout)
+        y_def, s_def = _conv5(C, xp, w, 2, B, H, cin, cout)
+        C.set_conv_stages(3, 0)
+        y_st3, s_st3 = _conv5(C, xp, w, 2, B, H, cin, cout)
+        assert torch.equal(y_st2, y_def) and torch.equal(y_def, y_st3)
+        assert torch.equal(s_st2, s_def) and torch.equal(s_def, s_st3)
+        # region mode 0 before and after a region_images call: neither the whole-image
+        # tiles (8x8) nor the row tiles (16x16) are on for the plain calls around it
+        bit = pack_tile(2, region_images=True)
+        assert region_ok(8, 2) == 0 and region_ok(16, 2) == 0 and region_ok(8, bit) == 0
+        y_a, _ = _conv5(C, xp, w, 2, B, H, cin, cout)
+        y_img, _ = _conv5(C, xp, w, bit, B, H, cin, cout)
+        assert region_ok(8, 2) == 0 and region_ok(16, 2) == 0 and region_ok(8, bit) == 0
+        y_b, _ = _conv5(C, xp, w, 2, B, H, cin, cout)
+        assert torch.equal(y_a, y_img) and torch.equal(y_a, y_b) and torch.equal(y_a, y_def)
+    finally:
+        C.set_conv_region(1)
+        C.set_conv_stages(3, 0)
+
+
+def test_conv_fwd_failed_call_disarms_side_job(C):
+    """A conv_fwd that throws in host validation (tile id 7, nothing launched)
+    takes the armed side job with it: the next streaming conv_fwd does not run
+    the update."""
+    dev = torch.device("cuda")
+    n = 1024
+    p = torch.randn(n, device=dev, generator=torch.Generator(device=dev).manual_seed(43))
+    p16 = p.to(torch.bfloat16)
+    grad = torch.ones(n, device=dev)
+    slot = torch.ones(1, device=dev)
+    p0, p16_0 = p.clone(), p16.clone()
+    B, H, cin, cout, tile = 2, 8, 64, 64, 1
+    x, w = _conv5_operands(B, H, cin, cout, 47)
+    xp = _pad(x)
+    C.set_conv_region(0)
+    try:
+        C.set_conv_side_sgd(p.data_ptr(), grad.data_ptr(), 0, p16.data_ptr(), slot.data_ptr(), 0.1, 0.0, 0.0, 0, n, [],
+                            [], [], [], 0, 0)
+        y = torch.empty(B, H, H, cout, dtype=torch.bfloat16, device=dev)
+        with pytest.raises(RuntimeError, match="bad tile id"):
+            C.conv_fwd(xp.data_ptr(), w.data_ptr(), y.data_ptr(), 0, 0, B, H, H, cin, cout, 5, 7, 1, _s())
+        y1, _ = _conv5(C, xp, w, tile, B, H, cin, cout, stats=False)
+        assert torch.equal(p, p0) and torch.equal(p16, p16_0)
+        y2, _ = _conv5(C, xp, w, tile, B, H, cin, cout, stats=False)
+        assert torch.equal(y1, y2)
+    finally:
+        C.set_conv_region(1)

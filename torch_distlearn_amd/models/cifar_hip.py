@@ -35,6 +35,7 @@ from typing import List, Optional
 import torch
 
 from .._native import native, stream_handle
+from ..ops.conv import pack_tile
 from ..ops.flat import HEADER, _lr_args
 from ..parallel.comm import runs_collectives
 from .cifar_convnet import BN_EPS, BN_MOMENTUM, KSIZE, CifarConvNet
@@ -160,7 +161,6 @@ class CifarHIPExecutor:
         self.bucket_updates_safe = True
         for i in range(self.nb):
             self.g32[self._leaf(i, 1)].zero_()
-        self.C.set_conv_stages(3, 0)
         # The dgrad convolutions run while the bucketed all-reduce is in flight
         # (the first bucket is launched after the last layer's wgrad).  With one
         # CU held by a workgroup of RCCL's footprint (19.7 KiB LDS, ~280
@@ -406,23 +406,16 @@ class CifarHIPExecutor:
             M = B * h * h
             w = self.w1p if i == 0 else self.p16[self._leaf(i, 0)]
             t, sp = self.fwd_plan[i]
-            if i == 0 and self.pair1:
-                t |= 1 << 24  # pair-packed weights (csrc FwdCfg bit 24)
             img = self.fwd_region_images and h * h < 128 and 128 % (h * h) == 0
-            if img:
-                C.set_conv_region(2)
-            try:
-                if self._fix_ok(B, h, cin, cout, t, sp):
-                    ntm = C.conv_fwd_fix(inp.data_ptr(), w.data_ptr(), self.y[i].data_ptr(),
-                                         self.stats[i].data_ptr() if train else 0, self.slabs.data_ptr(), B, h, h,
-                                         cin, cout, KSIZE, t, sp, 0, 0, 0, s)
-                else:
-                    ntm = C.conv_fwd(inp.data_ptr(), w.data_ptr(), self.y[i].data_ptr(),
+            t = pack_tile(t, pair=i == 0 and self.pair1, region_images=bool(img))
+            if self._fix_ok(B, h, cin, cout, t, sp):
+                ntm = C.conv_fwd_fix(inp.data_ptr(), w.data_ptr(), self.y[i].data_ptr(),
                                      self.stats[i].data_ptr() if train else 0, self.slabs.data_ptr(), B, h, h,
-                                     self.kin0 if i == 0 else cin, cout, KSIZE, t, sp, s)
-            finally:
-                if img:
-                    C.set_conv_region(1)
+                                     cin, cout, KSIZE, t, sp, 0, 0, 0, s)
+            else:
+                ntm = C.conv_fwd(inp.data_ptr(), w.data_ptr(), self.y[i].data_ptr(),
+                                 self.stats[i].data_ptr() if train else 0, self.slabs.data_ptr(), B, h, h,
+                                 self.kin0 if i == 0 else cin, cout, KSIZE, t, sp, s)
             fused = train and self.atomic  # coefficients derived by the consumer kernel
             if not fused:
                 C.bn_finalize(self.stats[i].data_ptr(), ntm, cout, M, self.p32[self._leaf(i, 2)].data_ptr(),
@@ -569,7 +562,7 @@ class CifarHIPExecutor:
             K = self.k1 if i == 0 else KSIZE * KSIZE * cin
             kcin = self.kin0 if i == 0 else cin
             tile, splits, direct = self.wplan[i]
-            wtile = tile | (1 << 24) if i == 0 and self.pair1 else tile  # pair-packed layer 1 (csrc make_geom_pair)
+            wtile = pack_tile(tile, pair=i == 0 and self.pair1)  # pair-packed layer 1 (csrc make_geom_pair)
             gw = self.g32[self._leaf(i, 0)]
             if i == 0 and self._side is not None and self._side["w"] is not None:
                 self._arm_side(self._side["w"])  # this launch also updates blocks 1 .. side block - 1
@@ -598,10 +591,9 @@ class CifarHIPExecutor:
                         self._ready(self._leaf(b, j))
             if i > 0:
                 dt, ds = self.dgrad_plan[i]
-                if self.dgrad_stages != 3:
-                    C.set_conv_stages(self.dgrad_stages, 0)
                 fix = self.fix >= 2 and self._fix_ok(B, h, cout, cin, dt, ds)
                 keep = self.fuse_combine and ds in (2, 4, 8, 16) and not fix
+                dt = pack_tile(dt, stages=self.dgrad_stages, keep_slabs=keep)
                 bnred = self.dgrad_bnred and ds == 1 and not keep and self._region_dgrad(i, B)
                 prt = self.bwd_rows[i - 1] if self.atomic else self.bwd_part[i - 1]
                 if bnred:
@@ -622,14 +614,11 @@ class CifarHIPExecutor:
                                                     prt.data_ptr(), s)
                     else:
                         C.conv_fwd(dY.data_ptr(), self.wt[i].data_ptr(), self.dP[i - 1].data_ptr(), 0,
-                                   self.slabs.data_ptr(), B, h, h, cout, cin, KSIZE, dt | ((1 << 20) if keep else 0),
-                                   ds, s)
+                                   self.slabs.data_ptr(), B, h, h, cout, cin, KSIZE, dt, ds, s)
                     if i in self._ride:
                         for j in range(4):
                             self._ready(self._leaf(i, j))
                 dp_splits = ds if keep else 0
-                if self.dgrad_stages != 3:
-                    C.set_conv_stages(3, 0)
         return self.loss[0]
 
     def policies(self) -> dict:

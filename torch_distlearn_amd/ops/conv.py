@@ -45,6 +45,22 @@ from .._native import native, stream_handle
 
 BF16 = torch.bfloat16
 
+
+def pack_tile(tile: int, stages: int = 0, waves: int = 0, keep_slabs: bool = False, pair: bool = False,
+              region_images: bool = False) -> int:
+    """The packed ``tile`` word of the native conv entry points (layout:
+    csrc/include/dl_ops.h above ``conv_fwd``).  ``stages`` / ``waves`` 0 keep
+    the process-wide setting; every value holds for the one call only."""
+    if not 0 <= tile <= 15:
+        raise ValueError(f"tile id {tile} outside 0..15")
+    if stages and not 2 <= stages <= 4:
+        raise ValueError("stages must be 0 (default) or 2..4")
+    if waves not in (0, 4, 8):
+        raise ValueError("waves must be 0 (default), 4 or 8")
+    return (tile | (stages << 4) | (waves << 8) | (bool(region_images) << 16) | (bool(keep_slabs) << 20)
+            | (bool(pair) << 24))
+
+
 class ShadowBinding:
     """What a conv module needs from the trainer: its bf16 shadow weight view,
     its fp32 gradient view, and a callback that reports the gradient ready.
@@ -110,7 +126,7 @@ def _plan_1x1(M: int, N: int, K: int):
     tile = 0 if N % 128 == 0 else 2
     stages = 3 if (N == 64 and K >= 256) else 2
     waves = 4 if (K <= 64 or (K <= 128 and N < 512)) else 8
-    return tile | (stages << 4) | (waves << 8), 1
+    return pack_tile(tile, stages=stages, waves=waves), 1
 
 
 def _wgrad_plan(cout: int, K: int, M: int):
@@ -292,7 +308,7 @@ def _plan_3x3(M: int, N: int, K: int):
     114.4 us with 8 (profiles/r5_conv3x3_sweep.jsonl)."""
     tile = 0 if N % 128 == 0 else 2
     waves = 4 if (N == 64 and _W4_C64) else 8
-    return tile | (2 << 4) | (waves << 8), 1
+    return pack_tile(tile, stages=2, waves=waves), 1
 
 
 _W4_C64 = True  # (r5_conv3x3_sweep.jsonl)

@@ -65,13 +65,13 @@ class ResNetHeadNLL(torch.autograd.Function):
         f = torch.empty(B, Cc, dtype=BF16, device=dev)
         loss = torch.empty(4, device=dev)
         C.head_pool(h.data_ptr(), f.data_ptr(), B, HW, Cc, loss.data_ptr(), s)
-        from .conv import _fwd_plan
+        from .conv import _fwd_plan, pack_tile
 
         tile, splits = _fwd_plan(B, NCp, Cc)
         splits = max(splits, 2)  # the fp32 slabs ARE the logits (never rounded to bf16)
         slab = torch.empty(splits * B * NCp, device=dev)
         C.conv_fwd(f.data_ptr(), wb.data_ptr(), f.data_ptr(), 0, slab.data_ptr(), B, 1, 1, Cc, NCp, 1,
-                   tile | (1 << 20), splits, s)
+                   pack_tile(tile, keep_slabs=True), splits, s)
         logp = torch.empty(B, ncls, device=dev)
         train = labels is not None and bind is not None
         if not train:
