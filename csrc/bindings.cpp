@@ -89,6 +89,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("conv_fwd_bnred", &conv_fwd_bnred);
   m.def("conv_fwd_fix", &conv_fwd_fix);
   m.def("conv_fix_ok", &conv_fix_ok);
+  m.def("conv_fwd_path", &conv_fwd_path, py::arg("B"), py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"),
+        py::arg("KS"), py::arg("tile"), py::arg("splits") = 1);
   m.def("conv_region_ok", &conv_region_ok, py::arg("B"), py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"),
         py::arg("KS"), py::arg("tile"), py::arg("splits") = 1);
   m.def("set_conv_fwd_pf", &set_conv_fwd_pf);

@@ -135,6 +135,10 @@ int conv_fwd_fix(uintptr_t x, uintptr_t w, uintptr_t y, uintptr_t stats, uintptr
                  int Cout, int KS, int tile, int splits, uintptr_t y_prev, uintptr_t coef, uintptr_t rows,
                  uintptr_t stream);
 int conv_fix_ok(int B, int H, int W, int Cin, int Cout, int KS, int tile, int splits);
+// Read-only: the kernel conv_fwd runs this call on, by run_fwd's own
+// predicates: 0 = streaming, 1 = region row tiles, 2 = region image tiles,
+// 3 = first-layer (c8) kernel; + 4 = position-major tiles (ops/conv.py PATH_*).
+int conv_fwd_path(int B, int H, int W, int Cin, int Cout, int KS, int tile, int splits = 1);
 int conv_fwd_bnred(uintptr_t x, uintptr_t w, uintptr_t y, int B, int H, int W, int Cin, int Cout, int KS, int tile,
                    uintptr_t y_prev, uintptr_t coef, uintptr_t rows, uintptr_t stream);
 int conv_fwd_ex(uintptr_t x, uintptr_t w, uintptr_t y, uintptr_t stats, uintptr_t slab, int B, int Ho, int Wo, int Hp,

@@ -154,11 +154,9 @@ struct FwdOpts {
   SgdJob side{};               // side job of this launch (streaming kernel only)
 };
 
-// Takes the armed side job, then decodes the tile word: the first statement
-// of every conv_fwd* entry point, so a call that throws leaves nothing armed.
-static FwdOpts fwd_opts(int tile) {
+// The tile word decoded (no side job): also what the read-only queries use.
+static FwdOpts decode_tile(int tile) {
   FwdOpts o;
-  o.side = take_side_job();
   o.tile = tile & 15;
   o.stages = (tile >> 4) & 15;
   o.waves = (tile >> 8) & 15;
@@ -167,6 +165,15 @@ static FwdOpts fwd_opts(int tile) {
   o.pair = (tile & kTilePair) != 0;
   if (o.stages && (o.stages < 2 || o.stages > 4)) throw std::runtime_error("conv_fwd: packed stages must be 2..4");
   if (o.waves && o.waves != 4 && o.waves != 8) throw std::runtime_error("conv_fwd: packed waves must be 4 or 8");
+  return o;
+}
+
+// Takes the armed side job, then decodes the tile word: the first statement
+// of every conv_fwd* entry point, so a call that throws leaves nothing armed.
+static FwdOpts fwd_opts(int tile) {
+  const SgdJob side = take_side_job();
+  FwdOpts o = decode_tile(tile);
+  o.side = side;
   return o;
 }
 
@@ -180,11 +187,20 @@ static FwdOpts fwd_opts(int tile) {
 static int g_posm = 1;
 void set_conv_posm(int on) { g_posm = on ? 1 : 0; }
 
+// Uniform taps (TAPU): every 64-channel K step of the streaming kernel lies in one tap.
+static bool fwd_tapu(const ConvGeom& g) { return g.Cin >= 64; }
+
+// Whether the streaming kernel with M tile bm runs this launch position-major
+// (tapu: fwd_tapu, the kernel's TAPU instance).
+static bool fwd_posm(const ConvGeom& g, int bm, bool tapu, bool addend) {
+  return g_posm && tapu && !addend && g.B % bm == 0 && (g.H < 2 * g.KS || g.W < 2 * g.KS) && g.S == 1 && !g.om &&
+         g.KH == g.KS && g.KW == g.KS && g.Hp == g.H + 2 * g.pad && g.Wp == g.W + 2 * g.pad;
+}
+
 template <int BM, int BN, bool TAPU, int ST, int WM, int WN>
 static void launch_fwd_w(ConvGeom& g, const FwdOpts& o, uintptr_t x, uintptr_t w, uintptr_t y, uintptr_t stats,
                          uintptr_t slab, int splits, hipStream_t s) {
-  g.posm = (g_posm && TAPU && !o.addend && g.B % BM == 0 && (g.H < 2 * g.KS || g.W < 2 * g.KS) && g.S == 1 && !g.om &&
-            g.KH == g.KS && g.KW == g.KS && g.Hp == g.H + 2 * g.pad && g.Wp == g.W + 2 * g.pad) ? 1 : 0;
+  g.posm = fwd_posm(g, BM, TAPU, o.addend != 0) ? 1 : 0;
   const int ntm = (g.M + BM - 1) / BM, ntn = (g.Cout + BN - 1) / BN;
   const int nkt = (g.Kch + 7) / 8;
   const int ktps = (nkt + splits - 1) / splits;
@@ -278,7 +294,7 @@ static void launch_fwd(ConvGeom& g, const FwdOpts& o, uintptr_t x, uintptr_t w, 
                        uintptr_t slab, int splits, hipStream_t s) {
   int st = o.stages ? o.stages : g_fwd_stages;
   if ((BM * 64 * 2 + BN * 64 * 2) * 4 > 160 * 1024) st = std::min(st, 3);
-  if (g.Cin >= 64) {
+  if (fwd_tapu(g)) {
     if (st == 2) launch_fwd_t<BM, BN, true, 2>(g, o, x, w, y, stats, slab, splits, s);
     else if (st == 3) launch_fwd_t<BM, BN, true, 3>(g, o, x, w, y, stats, slab, splits, s);
     else launch_fwd_t<BM, BN, true, 4>(g, o, x, w, y, stats, slab, splits, s);
@@ -424,10 +440,15 @@ void set_conv_c8_mt(int mt) {
   g_c8_mt = mt;
 }
 
-// The first-layer kernel (tile 2, unsplit, Cin 8 or the pair-packed 4) if the
-// shape takes it; false: it does not, nothing was launched.
-static bool launch_fwd_c8(const ConvGeom& g, const FwdOpts& o, uintptr_t x, uintptr_t w, uintptr_t y, uintptr_t stats,
-                          int splits, hipStream_t s) {
+// Launch plan of the first-layer kernel: M tiles per workgroup, region rows, LDS bytes.
+struct C8Plan {
+  int mt, rows;
+  size_t lds;
+};
+
+// Whether the first-layer kernel (tile 2, unsplit, Cin 8 or the pair-packed 4)
+// takes the shape, and its plan if so.
+static bool c8_plan(const ConvGeom& g, const FwdOpts& o, int splits, C8Plan& p) {
   const int H = g.H, W = g.W, KS = g.KS, Cout = g.Cout;
   // mt M tiles per workgroup (largest of g_c8_mt, ..., 2, 1 that keeps
   // >= 256 workgroups and divides the tiles of one image)
@@ -444,9 +465,15 @@ static bool launch_fwd_c8(const ConvGeom& g, const FwdOpts& o, uintptr_t x, uint
   const int c8_rslots = o.pair ? (c8_rows * g.Wp + 1) / 2 : c8_rows * g.Wp;  // 16-B region slots (pair: 2 pixels)
   const size_t c8_lds =
       (size_t)((c8_rslots + 2 + 63) / 64 * 64 + (64 * c8_chunks + 63) / 64 * 64) * 16 + 4 * 2 * 64 * 4;
-  if (!(o.tile == 2 && splits == 1 && g_region && g.pow2 && (g.Cin == 8 || o.pair) && W <= 128 && 128 % W == 0 &&
-        (H * W) % 128 == 0 && Cout % 64 == 0 && c8_lds <= 160 * 1024))
-    return false;
+  p = C8Plan{c8_mt, c8_rows, c8_lds};
+  return o.tile == 2 && splits == 1 && g_region && g.pow2 && (g.Cin == 8 || o.pair) && W <= 128 && 128 % W == 0 &&
+         (H * W) % 128 == 0 && Cout % 64 == 0 && c8_lds <= 160 * 1024;
+}
+
+static void launch_fwd_c8(const ConvGeom& g, const FwdOpts& o, const C8Plan& p, uintptr_t x, uintptr_t w, uintptr_t y,
+                          uintptr_t stats, hipStream_t s) {
+  const int Cout = g.Cout, c8_mt = p.mt, c8_rows = p.rows;
+  const size_t c8_lds = p.lds;
   const int grid = (g.M / 128 / c8_mt) * (Cout / 64);
   auto go = [&](auto kern) {
     static bool attr = false;
@@ -465,7 +492,30 @@ static bool launch_fwd_c8(const ConvGeom& g, const FwdOpts& o, uintptr_t x, uint
   } else {
     go(conv_fwd_c8_kernel<false>);
   }
-  return true;
+}
+
+// The kernel a forward / dgrad launch runs on (the values conv_fwd_path reports).
+enum class FwdKernel { Streaming = 0, RegionRows = 1, RegionImages = 2, C8 = 3 };
+
+// Host validation of a forward launch, shared by run_fwd and conv_fwd_path.
+static void check_fwd(const ConvGeom& g, const FwdOpts& o) {
+  if (g.Cout % 8 != 0) throw std::runtime_error("conv_fwd: Cout % 8 != 0");
+  if (o.tile > 2) throw std::runtime_error("conv_fwd: bad tile id");
+  if (g.Cout % fwd_bn(o.tile) != 0) throw std::runtime_error("conv_fwd: Cout must be a multiple of the N tile");
+}
+
+// Which kernel takes the launch, with its plan (rg: region tiles, c8: first layer).
+static FwdKernel pick_fwd(const ConvGeom& g, const FwdOpts& o, int splits, RegionGeom& rg, C8Plan& c8) {
+  // addends, the in-launch split-K combine and its BN reduce epilogue are on the streaming kernel
+  const bool streaming_only = o.fix || o.addend;
+  const bool images = g_region_images || o.region_images;
+  if (!streaming_only && c8_plan(g, o, splits, c8)) return FwdKernel::C8;
+  if (o.pair)
+    throw std::runtime_error("conv_fwd: pair-packed weights need the first-layer kernel (Cin 8, tile 2, no split)");
+  if (!streaming_only && ((o.tile == 0 && region_geom(g, 128, splits, images, rg)) ||
+                          (o.tile == 2 && region_geom(g, 64, splits, images, rg))))
+    return rg.rows_mode ? FwdKernel::RegionRows : FwdKernel::RegionImages;
+  return FwdKernel::Streaming;
 }
 
 // What every conv_fwd* entry point runs once it has its geometry and options:
@@ -477,26 +527,20 @@ static int run_fwd(ConvGeom& g, const FwdOpts& o, uintptr_t x, uintptr_t w, uint
   hipStream_t s = as_stream(stream);
   if (splits < 1) splits = 1;
   if (splits > 1 && !slab) throw std::runtime_error("conv_fwd: split-K needs a slab");
-  if (Cout % 8 != 0) throw std::runtime_error("conv_fwd: Cout % 8 != 0");
-  if (tile > 2) throw std::runtime_error("conv_fwd: bad tile id");
-  if (Cout % fwd_bn(tile) != 0) throw std::runtime_error("conv_fwd: Cout must be a multiple of the N tile");
+  check_fwd(g, o);
   RegionGeom rg{};
-  // addends, the in-launch split-K combine and its BN reduce epilogue are on the streaming kernel
-  const bool streaming_only = o.fix || o.addend;
-  const bool images = g_region_images || o.region_images;
-  bool streamed = false;
-  if (!streaming_only && launch_fwd_c8(g, o, x, w, y, stats, splits, s)) {
-    // ran on the first-layer kernel
-  } else if (o.pair) {
-    throw std::runtime_error("conv_fwd: pair-packed weights need the first-layer kernel (Cin 8, tile 2, no split)");
-  } else if (!streaming_only && tile == 0 && region_geom(g, 128, splits, images, rg)) {
+  C8Plan c8{};
+  const FwdKernel k = pick_fwd(g, o, splits, rg, c8);
+  const bool streamed = k == FwdKernel::Streaming;
+  if (k == FwdKernel::C8) {
+    launch_fwd_c8(g, o, c8, x, w, y, stats, s);
+  } else if (k != FwdKernel::Streaming && tile == 0) {
     if (g_region_waves == 4) launch_fwd_region<128, 2, 2>(g, rg, o, x, w, y, stats, slab, splits, s);
     else launch_fwd_region<128, 2, 4>(g, rg, o, x, w, y, stats, slab, splits, s);
-  } else if (!streaming_only && tile == 2 && region_geom(g, 64, splits, images, rg)) {
+  } else if (k != FwdKernel::Streaming) {
     if (g_region_waves == 4) launch_fwd_region<64, 2, 2>(g, rg, o, x, w, y, stats, slab, splits, s);
     else launch_fwd_region<64, 4, 2>(g, rg, o, x, w, y, stats, slab, splits, s);
   } else {
-    streamed = true;
     if (tile == 0) launch_fwd<128, 128>(g, o, x, w, y, stats, slab, splits, s);
     else if (tile == 1) launch_fwd<64, 64>(g, o, x, w, y, stats, slab, splits, s);
     else launch_fwd<128, 64>(g, o, x, w, y, stats, slab, splits, s);
@@ -531,6 +575,24 @@ int conv_fwd(uintptr_t x, uintptr_t w, uintptr_t y, uintptr_t stats, uintptr_t s
   if (o.pair && Cin != 4) throw std::runtime_error("conv_fwd: pair-packed weights need the 4-channel input");
   ConvGeom g = o.pair ? make_geom_pair(B, H, W, Cout, KS) : make_geom(B, H, W, Cin, Cout, KS);
   return run_fwd(g, o, x, w, y, stats, slab, splits, stream);
+}
+
+// Read-only: the kernel conv_fwd would run this call on, by the predicates of
+// run_fwd itself.  0 = streaming, 1 = region row tiles, 2 = region image tiles,
+// 3 = first-layer (c8) kernel; + 4: position-major tiles (streaming only).
+// Nothing is launched and no armed side job is taken.
+int conv_fwd_path(int B, int H, int W, int Cin, int Cout, int KS, int tile, int splits) {
+  const FwdOpts o = decode_tile(tile);
+  if (o.pair && Cin != 4) throw std::runtime_error("conv_fwd: pair-packed weights need the 4-channel input");
+  const ConvGeom g = o.pair ? make_geom_pair(B, H, W, Cout, KS) : make_geom(B, H, W, Cin, Cout, KS);
+  if (splits < 1) splits = 1;
+  check_fwd(g, o);
+  RegionGeom rg{};
+  C8Plan c8{};
+  const FwdKernel k = pick_fwd(g, o, splits, rg, c8);
+  int path = (int)k;
+  if (k == FwdKernel::Streaming && fwd_posm(g, fwd_bm(o.tile), fwd_tapu(g), false)) path |= 4;
+  return path;
 }
 
 // The next streaming conv_fwd launch also runs the fused SGD update of the

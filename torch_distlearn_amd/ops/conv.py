@@ -45,6 +45,10 @@ from .._native import native, stream_handle
 
 BF16 = torch.bfloat16
 
+# What the native ``conv_fwd_path`` query returns: the kernel conv_fwd runs a
+# call on, plus PATH_POSM for the streaming kernel's position-major tiles.
+PATH_STREAMING, PATH_REGION_ROWS, PATH_REGION_IMAGES, PATH_FIRST_LAYER, PATH_POSM = 0, 1, 2, 3, 4
+
 
 def pack_tile(tile: int, stages: int = 0, waves: int = 0, keep_slabs: bool = False, pair: bool = False,
               region_images: bool = False) -> int:
