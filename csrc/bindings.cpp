@@ -13,6 +13,10 @@ using namespace dl;
 PYBIND11_MODULE(_C, m) {
   m.doc() = "distlearn MI355X (gfx950) native kernels, RCCL communicator and data runtime";
 
+  // per-call values, opaque to Python: built by side_sgd_job / side_reduce_job / next_prep
+  py::class_<SideJob>(m, "SideJob");
+  py::class_<NextPrep>(m, "NextPrep");
+
   // ---- flat bucket kernels --------------------------------------------------
   m.def("sgd_update", &sgd_update, py::arg("p"), py::arg("g"), py::arg("mom"), py::arg("p16"), py::arg("slot"),
         py::arg("lr"), py::arg("momentum"), py::arg("wd"), py::arg("n"), py::arg("stream"), py::arg("lr_dev") = 0);
@@ -33,16 +37,13 @@ PYBIND11_MODULE(_C, m) {
   m.def("sgd_update_slabs", &sgd_update_slabs, py::arg("p"), py::arg("g"), py::arg("mom"), py::arg("p16"),
         py::arg("slot"), py::arg("lr"), py::arg("momentum"), py::arg("wd"), py::arg("n"), py::arg("offs"),
         py::arg("lens"), py::arg("slabs"), py::arg("splits"), py::arg("tail"), py::arg("tail_slab"),
-        py::arg("skip_lo"), py::arg("skip_hi"), py::arg("stream"), py::arg("lr_dev") = 0);
-  m.def("arm_sgd_next_prep", &arm_sgd_next_prep);
-  m.def("sgd_next_prep_armed", &sgd_next_prep_armed);
-  m.def("set_sgd_trim", &set_sgd_trim);
-  m.def("disarm_sgd_next_prep", &disarm_sgd_next_prep);
-  m.def("set_conv_side_sgd", &set_conv_side_sgd, py::arg("p"), py::arg("g"), py::arg("mom"), py::arg("p16"),
-        py::arg("slot"), py::arg("lr"), py::arg("momentum"), py::arg("wd"), py::arg("lo"), py::arg("hi"),
-        py::arg("offs"), py::arg("lens"), py::arg("slabs"), py::arg("splits"), py::arg("nblk"),
-        py::arg("lr_dev") = 0);
-  m.def("set_conv_side_reduce", &set_conv_side_reduce);
+        py::arg("skip_lo"), py::arg("skip_hi"), py::arg("stream"), py::arg("lr_dev") = 0,
+        py::arg("next_prep") = py::none());
+  m.def("next_prep", &next_prep);
+  m.def("side_sgd_job", &side_sgd_job, py::arg("p"), py::arg("g"), py::arg("mom"), py::arg("p16"), py::arg("slot"),
+        py::arg("lr"), py::arg("momentum"), py::arg("wd"), py::arg("lo"), py::arg("hi"), py::arg("offs"),
+        py::arg("lens"), py::arg("slabs"), py::arg("splits"), py::arg("nblk"), py::arg("lr_dev") = 0);
+  m.def("side_reduce_job", &side_reduce_job);
   m.def("slab_reduce_multi", &slab_reduce_multi);
   m.def("confusion_update", &confusion_update);
   m.def("bn_nhwc_fwd", &bn_nhwc_fwd);
@@ -66,7 +67,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("gather_normalize", &gather_normalize);
 
   // ---- convnet kernels (MFMA implicit GEMM, BN/ReLU/pool, classifier head) ------
-  m.def("conv_fwd", &conv_fwd);
+  m.def("conv_fwd", &conv_fwd, py::arg("x"), py::arg("w"), py::arg("y"), py::arg("stats"), py::arg("slab"),
+        py::arg("B"), py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"), py::arg("KS"), py::arg("tile"),
+        py::arg("splits"), py::arg("stream"), py::arg("side") = py::none());
   m.def("conv_fwd_add", &conv_fwd_add, py::arg("x"), py::arg("w"), py::arg("y"), py::arg("addend"), py::arg("B"),
         py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"), py::arg("KS"), py::arg("tile"), py::arg("stream"),
         py::arg("addend_mask") = 0);
@@ -81,13 +84,18 @@ PYBIND11_MODULE(_C, m) {
   m.def("set_conv_c8_mt", &set_conv_c8_mt);
   m.def("set_conv_waves", &set_conv_waves);
   m.def("set_conv_debug", &set_conv_debug);
-  m.def("conv_wgrad", &conv_wgrad);
+  m.def("conv_wgrad", &conv_wgrad, py::arg("dy"), py::arg("x"), py::arg("out"), py::arg("B"), py::arg("H"),
+        py::arg("W"), py::arg("Cin"), py::arg("Cout"), py::arg("KS"), py::arg("splits"), py::arg("ldo"),
+        py::arg("tile"), py::arg("atomic_creal"), py::arg("stream"), py::arg("side") = py::none());
   m.def("combine_bwd_reduce", &combine_bwd_reduce);
   m.def("bn_bwd_apply_head", &bn_bwd_apply_head);
   m.def("combine_bwd_reduce_blocks", &combine_bwd_reduce_blocks);
   m.def("conv_fwd_ex", &conv_fwd_ex);
   m.def("conv_fwd_bnred", &conv_fwd_bnred);
-  m.def("conv_fwd_fix", &conv_fwd_fix);
+  m.def("conv_fwd_fix", &conv_fwd_fix, py::arg("x"), py::arg("w"), py::arg("y"), py::arg("stats"), py::arg("slab"),
+        py::arg("B"), py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"), py::arg("KS"), py::arg("tile"),
+        py::arg("splits"), py::arg("y_prev"), py::arg("coef"), py::arg("rows"), py::arg("stream"),
+        py::arg("side") = py::none());
   m.def("conv_fix_ok", &conv_fix_ok);
   m.def("conv_fwd_path", &conv_fwd_path, py::arg("B"), py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"),
         py::arg("KS"), py::arg("tile"), py::arg("splits") = 1);

@@ -26,43 +26,64 @@ void stamp_time(uintptr_t slot, uintptr_t stream);
 int wall_clock_khz();
 void cast_f32_bf16(uintptr_t x, uintptr_t y, int64_t n, uintptr_t stream);
 void cast_bf16_f32(uintptr_t x, uintptr_t y, int64_t n, uintptr_t stream);
-// the next streaming conv_fwd launch also runs the SGD of flat elements [lo, hi)
-// as nblk extra workgroups (conv_igemm.hip; flat_ops' update then skips them)
-void set_conv_side_sgd(uintptr_t p, uintptr_t g, uintptr_t mom, uintptr_t p16, uintptr_t slot, float lr,
-                       float momentum, float wd, int64_t lo, int64_t hi, std::vector<int64_t> offs,
-                       std::vector<int64_t> lens, std::vector<uintptr_t> slabs, std::vector<int> splits, int nblk,
-                       uintptr_t lr_dev = 0);
-// ... or sums split-K weight-gradient slabs into the gradient buffer g instead
-// (reduce-only side job: a multi-node step's gradients before the all-reduce)
-void set_conv_side_reduce(uintptr_t g, int64_t lo, int64_t hi, std::vector<int64_t> offs, std::vector<int64_t> lens,
-                          std::vector<uintptr_t> slabs, std::vector<int> splits, int nblk);
+// Side job of one streaming conv launch (`side` of conv_fwd / conv_fwd_fix /
+// conv_wgrad): nblk extra workgroups (0: one float4 per thread) that run the SGD
+// of flat elements [lo, hi) (flat_ops' update then skips them) -- or, reduce-only,
+// sum split-K weight-gradient slabs into the gradient buffer g (a multi-node
+// step's gradients before the all-reduce).  Every check runs in the two builders
+// (conv_igemm.hip), so a bad job fails before any launch; never modified after.
+struct SideJob {
+  const bool reduce;
+  const uintptr_t p, g, mom, p16, slot;
+  const float lr, momentum, wd;
+  const int64_t lo, hi;
+  const std::vector<int64_t> offs, lens;
+  const std::vector<uintptr_t> slabs;
+  const std::vector<int> splits;
+  const int nblk;
+  const uintptr_t lr_dev;
+};
+SideJob side_sgd_job(uintptr_t p, uintptr_t g, uintptr_t mom, uintptr_t p16, uintptr_t slot, float lr, float momentum,
+                     float wd, int64_t lo, int64_t hi, std::vector<int64_t> offs, std::vector<int64_t> lens,
+                     std::vector<uintptr_t> slabs, std::vector<int> splits, int nblk, uintptr_t lr_dev = 0);
+SideJob side_reduce_job(uintptr_t g, int64_t lo, int64_t hi, std::vector<int64_t> offs, std::vector<int64_t> lens,
+                        std::vector<uintptr_t> slabs, std::vector<int> splits, int nblk);
 void sgd_update_g16(uintptr_t p, uintptr_t g16, uintptr_t mom, uintptr_t p16, uintptr_t slot, float lr,
                     float momentum, float wd, int64_t n, uintptr_t stream, uintptr_t lr_dev = 0);
 // sgd_update whose gradient in up to 4 ranges [offs, offs+lens) is the sum of the
 // split-K slabs [splits][lens] at slabs[j], and in one optional channel-padded
 // "tail" range (offset, numel, splits, Cout, taps, Cp, C) the sum of tail_slab
 // (bitwise slab_reduce's sums); elements [skip_lo, skip_hi) are left alone (a
-// conv launch's side job updated them: set_conv_side_sgd)
+// conv launch's side job updated them: SideJob).  next: the launch also prepares
+// the next step of an unrolled graph -- gathers its batch into xp, zeroes its
+// accumulators (prep_dev.h) and writes the first layer's updated weights into the
+// packed bf16 operand w1p (from the slab tail, or from the main loop's elements
+// [pack_off, +pack_len)).  Checked when next_prep builds it; never modified after.
+struct NextPrep {
+  const uintptr_t img, order, lab_all, lab_out, ctr;
+  const int n_order, B, C;
+  const std::vector<float> mean, stdv;
+  const uintptr_t xp;
+  const int Cp, H, W, sp;
+  const std::vector<uintptr_t> zp;
+  const std::vector<int64_t> zn;
+  const uintptr_t w1p;
+  const int w1_cp;
+  const int64_t pack_off, pack_len;
+};
+NextPrep next_prep(uintptr_t img, uintptr_t order, uintptr_t lab_all, uintptr_t lab_out, uintptr_t ctr, int n_order,
+                   int B, int C, std::vector<float> mean, std::vector<float> stdv, uintptr_t xp, int Cp, int H, int W,
+                   int sp, std::vector<uintptr_t> zp, std::vector<int64_t> zn, uintptr_t w1p, int w1_cp,
+                   int64_t pack_off, int64_t pack_len);
 void sgd_update_slabs(uintptr_t p, uintptr_t g, uintptr_t mom, uintptr_t p16, uintptr_t slot, float lr,
                       float momentum, float wd, int64_t n, std::vector<int64_t> offs, std::vector<int64_t> lens,
                       std::vector<uintptr_t> slabs, std::vector<int> splits, std::vector<int64_t> tail,
                       uintptr_t tail_slab, int64_t skip_lo, int64_t skip_hi, uintptr_t stream,
-                      uintptr_t lr_dev = 0);
-// one-shot: the next sgd_update_slabs launch also prepares the next step of an
-// unrolled graph -- gathers its batch into xp, zeroes its accumulators (prep_dev.h)
-// and writes the first layer's updated weights into the packed bf16 operand w1p
-// (from the slab tail, or from the main loop's elements [pack_off, +pack_len))
-void arm_sgd_next_prep(uintptr_t img, uintptr_t order, uintptr_t lab_all, uintptr_t lab_out, uintptr_t ctr,
-                       int n_order, int B, int C, std::vector<float> mean, std::vector<float> stdv, uintptr_t xp,
-                       int Cp, int H, int W, int sp, std::vector<uintptr_t> zp, std::vector<int64_t> zn,
-                       uintptr_t w1p, int w1_cp, int64_t pack_off, int64_t pack_len);
-bool sgd_next_prep_armed();
+                      uintptr_t lr_dev = 0, const NextPrep* next = nullptr);
 // reduce-only launch: split-K slabs of up to 4 ranges + 1 padded tail summed into g
 void slab_reduce_multi(uintptr_t g, int64_t n, std::vector<int64_t> offs, std::vector<int64_t> lens,
                        std::vector<uintptr_t> slabs, std::vector<int> splits, std::vector<int64_t> tail,
                        uintptr_t tail_slab, uintptr_t stream);
-void set_sgd_trim(bool on);  // update grid sized to the elements before a skipped suffix (default on)
-void disarm_sgd_next_prep();
 
 // metrics.hip ---------------------------------------------------------------
 // channels-last training BatchNorm (+ReLU, +residual) for the ResNet-50 path
@@ -115,8 +136,10 @@ void gather_normalize(uintptr_t images, uintptr_t idx, uintptr_t out, int B, int
 //   bit 24     pair-packed first-layer weights over the 4-channel input
 //              (conv_fwd's first-layer kernel and conv_wgrad; dl_common.h pack1_index)
 // conv_wgrad's tile is 1 = 64x64 or 2 = 128x128 (Cout x K) plus bit 24.
+// side (conv_fwd, conv_fwd_fix, conv_wgrad): the launch's side job; one that the
+// kernel the call takes cannot carry (region, first layer) throws before any launch
 int conv_fwd(uintptr_t x, uintptr_t w, uintptr_t y, uintptr_t stats, uintptr_t slab, int B, int H, int W, int Cin,
-             int Cout, int KS, int tile, int splits, uintptr_t stream);
+             int Cout, int KS, int tile, int splits, uintptr_t stream, const SideJob* side = nullptr);
 int conv_fwd_stat_rows(int B, int H, int W, int Cin, int Cout, int KS, int tile, int splits);
 void set_conv_region(int on);
 void set_bn_bwd_items(int n);
@@ -133,7 +156,7 @@ void set_conv_wgrad_stamps(uintptr_t buf);
 int conv_region_ok(int B, int H, int W, int Cin, int Cout, int KS, int tile, int splits = 1);
 int conv_fwd_fix(uintptr_t x, uintptr_t w, uintptr_t y, uintptr_t stats, uintptr_t slab, int B, int H, int W, int Cin,
                  int Cout, int KS, int tile, int splits, uintptr_t y_prev, uintptr_t coef, uintptr_t rows,
-                 uintptr_t stream);
+                 uintptr_t stream, const SideJob* side = nullptr);
 int conv_fix_ok(int B, int H, int W, int Cin, int Cout, int KS, int tile, int splits);
 // Read-only: the kernel conv_fwd runs this call on, by run_fwd's own
 // predicates: 0 = streaming, 1 = region row tiles, 2 = region image tiles,
@@ -148,7 +171,7 @@ void conv_wgrad_ex(uintptr_t dy, uintptr_t x, uintptr_t out, int B, int Ho, int 
                    int dpad, int Cin, int Cout, int KH, int KW, int S, int splits, int ldo, int tile,
                    uintptr_t stream);
 void conv_wgrad(uintptr_t dy, uintptr_t x, uintptr_t out, int B, int H, int W, int Cin, int Cout, int KS, int splits,
-                int ldo, int tile, int atomic_creal, uintptr_t stream);
+                int ldo, int tile, int atomic_creal, uintptr_t stream, const SideJob* side = nullptr);
 void set_reduce_atomic_conv(int rows);
 void conv_fwd_add(uintptr_t x, uintptr_t w, uintptr_t y, uintptr_t addend, int B, int H, int W, int Cin, int Cout,
                   int KS, int tile, uintptr_t stream, uintptr_t addend_mask = 0);

@@ -25,7 +25,7 @@ __global__ void __launch_bounds__(64 * WM * WN) conv_fwd_kernel(const bf16_t* __
                                                        const BnRedArgs br = BnRedArgs{},
                                                        const SgdJob side = SgdJob{},
                                                        int* __restrict__ fixcnt = nullptr) {
-  // side job (set_conv_side_sgd): the last side.nblk workgroups run part of
+  // side job (dl_ops.h SideJob): the last side.nblk workgroups run part of
   // the step's SGD update on the CUs the convolution's one-workgroup-per-CU
   // grid leaves free (its gradients are final by the time this conv runs)
   const int conv_grid = (int)gridDim.x - side.nblk;

@@ -116,17 +116,38 @@ int conv_fwd_stat_rows(int B, int H, int W, int Cin, int Cout, int KS, int tile,
   return (g.M + rpb - 1) / rpb;
 }
 
-// Cross-call state: the one-shot side job armed by set_conv_side_sgd /
-// set_conv_side_reduce for the next conv_fwd / conv_wgrad call, and the
-// round-robin cursor over the arrival counters g_fix_cnt.
-static SgdJob g_side_sgd{};
+// The only cross-call state: the round-robin cursor over the arrival counters g_fix_cnt.
 static int g_fix_next = 0;
 
-// The armed side job, disarmed: whatever the call that takes it goes on to do
-// (launch it, or throw), nothing stays armed for the next conv.
-static SgdJob take_side_job() {
-  const SgdJob j = g_side_sgd;
-  g_side_sgd.nblk = 0;
+// The kernel argument of a call's side job (none: nblk 0).  Runs every check of
+// make_sgd_job / make_reduce_job, which is how the builders below validate.
+static SgdJob side_job(const SideJob* s) {
+  if (!s) return SgdJob{};
+  SgdJob j = s->reduce ? make_reduce_job(s->g, s->lo, s->hi, s->offs, s->lens, s->slabs, s->splits, {}, 0)
+                       : make_sgd_job(s->p, s->g, s->mom, s->p16, s->slot, s->lr, s->momentum, s->wd, s->lo, s->hi,
+                                      s->offs, s->lens, s->slabs, s->splits, {}, 0, s->lr_dev);
+  j.nblk = s->nblk > 0 ? s->nblk : -1;  // -1: sized by the launch (one float4 per thread)
+  return j;
+}
+
+// The fused SGD update of the elements [lo, hi) of the flat buffer p: gradient g,
+// or the split-K slabs of the given ranges; bf16 shadow p16 required (dl_ops.h SideJob).
+SideJob side_sgd_job(uintptr_t p, uintptr_t g, uintptr_t mom, uintptr_t p16, uintptr_t slot, float lr, float momentum,
+                     float wd, int64_t lo, int64_t hi, std::vector<int64_t> offs, std::vector<int64_t> lens,
+                     std::vector<uintptr_t> slabs, std::vector<int> splits, int nblk, uintptr_t lr_dev) {
+  if (!p16) throw std::runtime_error("side_sgd_job: needs the bf16 shadow");
+  const SideJob j{false, p, g, mom, p16, slot, lr, momentum, wd, lo, hi, offs, lens, slabs, splits, nblk, lr_dev};
+  side_job(&j);
+  return j;
+}
+
+// The sums of the split-K weight-gradient slabs of the given in-place ranges into
+// the gradient buffer g (sgd_dev.h: bitwise slab_reduce's sums), not in a launch of their own.
+SideJob side_reduce_job(uintptr_t g, int64_t lo, int64_t hi, std::vector<int64_t> offs, std::vector<int64_t> lens,
+                        std::vector<uintptr_t> slabs, std::vector<int> splits, int nblk) {
+  if (offs.empty()) throw std::runtime_error("side_reduce_job: no slab range");
+  const SideJob j{true, 0, g, 0, 0, 0, 0.f, 0.f, 0.f, lo, hi, offs, lens, slabs, splits, nblk, 0};
+  side_job(&j);
   return j;
 }
 
@@ -139,7 +160,7 @@ static int g_fwd_stages = 3;
 constexpr int kTileRegionImages = 1 << 16, kTileKeepSlabs = 1 << 20, kTilePair = 1 << 24;
 
 // Everything that is per call in a forward / dgrad launch: the decoded tile
-// word (fwd_opts) plus what the entry point's own arguments add.
+// word (decode_tile) plus what the entry point's own arguments add.
 struct FwdOpts {
   int tile = 0;                // 0 = 128x128, 1 = 64x64, 2 = 128x64
   int stages = 0, waves = 0;   // streaming kernel; 0 = the process setting
@@ -154,7 +175,8 @@ struct FwdOpts {
   SgdJob side{};               // side job of this launch (streaming kernel only)
 };
 
-// The tile word decoded (no side job): also what the read-only queries use.
+// The tile word decoded: the first statement of every conv_fwd* entry point,
+// and what the read-only queries use.
 static FwdOpts decode_tile(int tile) {
   FwdOpts o;
   o.tile = tile & 15;
@@ -165,15 +187,6 @@ static FwdOpts decode_tile(int tile) {
   o.pair = (tile & kTilePair) != 0;
   if (o.stages && (o.stages < 2 || o.stages > 4)) throw std::runtime_error("conv_fwd: packed stages must be 2..4");
   if (o.waves && o.waves != 4 && o.waves != 8) throw std::runtime_error("conv_fwd: packed waves must be 4 or 8");
-  return o;
-}
-
-// Takes the armed side job, then decodes the tile word: the first statement
-// of every conv_fwd* entry point, so a call that throws leaves nothing armed.
-static FwdOpts fwd_opts(int tile) {
-  const SgdJob side = take_side_job();
-  FwdOpts o = decode_tile(tile);
-  o.side = side;
   return o;
 }
 
@@ -531,7 +544,8 @@ static int run_fwd(ConvGeom& g, const FwdOpts& o, uintptr_t x, uintptr_t w, uint
   RegionGeom rg{};
   C8Plan c8{};
   const FwdKernel k = pick_fwd(g, o, splits, rg, c8);
-  const bool streamed = k == FwdKernel::Streaming;
+  if (o.side.nblk != 0 && k != FwdKernel::Streaming)  // nothing is enqueued yet
+    throw std::runtime_error("conv_fwd: a side job needs the streaming kernel (this call: region / first layer)");
   if (k == FwdKernel::C8) {
     launch_fwd_c8(g, o, c8, x, w, y, stats, s);
   } else if (k != FwdKernel::Streaming && tile == 0) {
@@ -546,8 +560,6 @@ static int run_fwd(ConvGeom& g, const FwdOpts& o, uintptr_t x, uintptr_t w, uint
     else launch_fwd<128, 64>(g, o, x, w, y, stats, slab, splits, s);
   }
   DL_HIP_CHECK(hipGetLastError());
-  if (o.side.nblk != 0 && !streamed)  // armed, but this call ran on the region / c8 kernel
-    throw std::runtime_error("set_conv_side_sgd: the next conv_fwd call must run on the streaming kernel");
   if (splits == 1 || o.fix) return (g.M + fwd_bm(tile) - 1) / fwd_bm(tile);
   if (o.keep_slabs) {
     if (stats) throw std::runtime_error("conv_fwd keep-slabs: no statistics");
@@ -570,8 +582,9 @@ static int run_fwd(ConvGeom& g, const FwdOpts& o, uintptr_t x, uintptr_t w, uint
 // per-call bits of dl_ops.h.  splits > 1: split-K into `slab` (fp32
 // [splits][M][Cout]) + combine (bf16 y, BN partials).
 int conv_fwd(uintptr_t x, uintptr_t w, uintptr_t y, uintptr_t stats, uintptr_t slab, int B, int H, int W, int Cin,
-             int Cout, int KS, int tile, int splits, uintptr_t stream) {
-  const FwdOpts o = fwd_opts(tile);
+             int Cout, int KS, int tile, int splits, uintptr_t stream, const SideJob* side) {
+  FwdOpts o = decode_tile(tile);
+  o.side = side_job(side);
   if (o.pair && Cin != 4) throw std::runtime_error("conv_fwd: pair-packed weights need the 4-channel input");
   ConvGeom g = o.pair ? make_geom_pair(B, H, W, Cout, KS) : make_geom(B, H, W, Cin, Cout, KS);
   return run_fwd(g, o, x, w, y, stats, slab, splits, stream);
@@ -580,7 +593,7 @@ int conv_fwd(uintptr_t x, uintptr_t w, uintptr_t y, uintptr_t stats, uintptr_t s
 // Read-only: the kernel conv_fwd would run this call on, by the predicates of
 // run_fwd itself.  0 = streaming, 1 = region row tiles, 2 = region image tiles,
 // 3 = first-layer (c8) kernel; + 4: position-major tiles (streaming only).
-// Nothing is launched and no armed side job is taken.
+// Nothing is launched.
 int conv_fwd_path(int B, int H, int W, int Cin, int Cout, int KS, int tile, int splits) {
   const FwdOpts o = decode_tile(tile);
   if (o.pair && Cin != 4) throw std::runtime_error("conv_fwd: pair-packed weights need the 4-channel input");
@@ -593,35 +606,6 @@ int conv_fwd_path(int B, int H, int W, int Cin, int Cout, int KS, int tile, int 
   int path = (int)k;
   if (k == FwdKernel::Streaming && fwd_posm(g, fwd_bm(o.tile), fwd_tapu(g), false)) path |= 4;
   return path;
-}
-
-// The next streaming conv_fwd launch also runs the fused SGD update of the
-// elements [lo, hi) of the flat buffer p (gradient g, or the split-K slabs of
-// the given ranges; bf16 shadow p16 required) as nblk extra workgroups
-// (0: one float4 per thread).  One-shot; the caller's final update skips [lo, hi).
-// lr_dev != 0: the rate is read from that device fp32 instead of lr (sgd_dev.h sgd_rate).
-void set_conv_side_sgd(uintptr_t p, uintptr_t g, uintptr_t mom, uintptr_t p16, uintptr_t slot, float lr,
-                       float momentum, float wd, int64_t lo, int64_t hi, std::vector<int64_t> offs,
-                       std::vector<int64_t> lens, std::vector<uintptr_t> slabs, std::vector<int> splits, int nblk,
-                       uintptr_t lr_dev) {
-  if (!p16) throw std::runtime_error("set_conv_side_sgd: needs the bf16 shadow");
-  SgdJob j = make_sgd_job(p, g, mom, p16, slot, lr, momentum, wd, lo, hi, offs, lens, slabs, splits, {}, 0, lr_dev);
-  j.nblk = nblk > 0 ? nblk : -1;  // -1: sized by the launch (one float4 per thread)
-  g_side_sgd = j;
-}
-
-// The next streaming conv_fwd launch sums the split-K weight-gradient slabs of
-// the given in-place ranges into the gradient buffer g (a reduce-only side job,
-// sgd_dev.h: bitwise slab_reduce's sums) as nblk extra workgroups (0: one
-// float4 per thread): a multi-node step's weight gradient, materialised for
-// its all-reduce on the CUs the dgrad leaves free instead of in a launch of
-// its own.  One-shot.
-void set_conv_side_reduce(uintptr_t g, int64_t lo, int64_t hi, std::vector<int64_t> offs, std::vector<int64_t> lens,
-                          std::vector<uintptr_t> slabs, std::vector<int> splits, int nblk) {
-  if (offs.empty()) throw std::runtime_error("set_conv_side_reduce: no slab range");
-  SgdJob j = make_reduce_job(g, lo, hi, offs, lens, slabs, splits, {}, 0);
-  j.nblk = nblk > 0 ? nblk : -1;
-  g_side_sgd = j;
 }
 
 // Whether conv_fwd runs this unsplit shape on the region (tap-reuse) kernel --
@@ -638,7 +622,7 @@ int conv_region_ok(int B, int H, int W, int Cin, int Cout, int KS, int tile, int
 // rows written (M tiles, mode 0) or throws if the shape takes another kernel.
 int conv_fwd_bnred(uintptr_t x, uintptr_t w, uintptr_t y, int B, int H, int W, int Cin, int Cout, int KS, int tile,
                    uintptr_t y_prev, uintptr_t coef, uintptr_t rows, uintptr_t stream) {
-  FwdOpts o = fwd_opts(tile);
+  FwdOpts o = decode_tile(tile);
   ConvGeom g = make_geom(B, H, W, Cin, Cout, KS);
   RegionGeom rg{};
   if (o.pair || !any_region_geom(g, tile, 1, rg))
@@ -656,8 +640,9 @@ int conv_fwd_bnred(uintptr_t x, uintptr_t w, uintptr_t y, int B, int H, int W, i
 // (conv_fix_ok).  Returns the rows written (M tiles).
 int conv_fwd_fix(uintptr_t x, uintptr_t w, uintptr_t y, uintptr_t stats, uintptr_t slab, int B, int H, int W, int Cin,
                  int Cout, int KS, int tile, int splits, uintptr_t y_prev, uintptr_t coef, uintptr_t rows,
-                 uintptr_t stream) {
-  FwdOpts o = fwd_opts(tile);
+                 uintptr_t stream, const SideJob* side) {
+  FwdOpts o = decode_tile(tile);
+  o.side = side_job(side);
   if (splits < 2 || !slab) throw std::runtime_error("conv_fwd_fix: a split-K plan with a slab");
   if ((y_prev != 0) != (rows != 0) || (y_prev && !coef)) throw std::runtime_error("conv_fwd_fix: BN reduce operands");
   o.fix = true;
@@ -678,7 +663,7 @@ int conv_fix_ok(int B, int H, int W, int Cin, int Cout, int KS, int tile, int sp
 // (KS = 1 or the region kernels disabled for the shape), no split-K / stats.
 void conv_fwd_add(uintptr_t x, uintptr_t w, uintptr_t y, uintptr_t addend, int B, int H, int W, int Cin, int Cout,
                   int KS, int tile, uintptr_t stream, uintptr_t addend_mask) {
-  FwdOpts o = fwd_opts(tile);
+  FwdOpts o = decode_tile(tile);
   ConvGeom g = make_geom(B, H, W, Cin, Cout, KS);
   if (!addend) throw std::runtime_error("conv_fwd_add: null addend");
   if (KS != 1 && g_region) throw std::runtime_error("conv_fwd_add: only the streaming kernel (KS = 1)");
@@ -693,7 +678,7 @@ void conv_fwd_add(uintptr_t x, uintptr_t w, uintptr_t y, uintptr_t addend, int B
 int conv_fwd_ex(uintptr_t x, uintptr_t w, uintptr_t y, uintptr_t stats, uintptr_t slab, int B, int Ho, int Wo, int Hp,
                 int Wp, int Cin, int Cout, int KH, int KW, int S, int om_S, int om_H0, int om_W0, int om_W, int om_HW,
                 uintptr_t addend, int tile, int splits, uintptr_t stream) {
-  FwdOpts o = fwd_opts(tile);
+  FwdOpts o = decode_tile(tile);
   ConvGeom g = make_geom_ex(B, Ho, Wo, Hp, Wp, Cin, Cout, KH, KW, S);
   if (om_S > 0) {
     g.om = 1; g.omS = om_S; g.omH0 = om_H0; g.omW0 = om_W0; g.omW = om_W; g.omHW = om_HW;
@@ -709,8 +694,8 @@ int conv_fwd_ex(uintptr_t x, uintptr_t w, uintptr_t y, uintptr_t stats, uintptr_
 
 // out: fp32 [splits][Cout][ldo], ldo >= K (K = KS*KS*Cin); tile 1 = 64x64, 2 = 128x128 (co x k)
 static void conv_wgrad_g(const ConvGeom& g, uintptr_t dy, uintptr_t x, uintptr_t out, int splits, int ldo, int tile,
-                         uintptr_t stream) {
-  SgdJob side = take_side_job();
+                         uintptr_t stream, const SideJob* side_in = nullptr) {
+  SgdJob side = side_job(side_in);
   const int Cout = g.Cout, W = g.W;
   if (tile != 1 && tile != 2) throw std::runtime_error("conv_wgrad: tile 1 (64x64) or 2 (128x128)");
   if (ldo < g.K) throw std::runtime_error("conv_wgrad: ldo < K");
@@ -738,14 +723,14 @@ static void conv_wgrad_g(const ConvGeom& g, uintptr_t dy, uintptr_t x, uintptr_t
 }
 
 void conv_wgrad(uintptr_t dy, uintptr_t x, uintptr_t out, int B, int H, int W, int Cin, int Cout, int KS, int splits,
-                int ldo, int tile, int atomic_creal, uintptr_t stream) {
+                int ldo, int tile, int atomic_creal, uintptr_t stream, const SideJob* side) {
   if (atomic_creal != 0) throw std::runtime_error("conv_wgrad: atomic split-K was removed in round 6 (pass 0)");
   if (tile & kTilePair) {  // pair-packed first layer (make_geom_pair): x is [B][Hp][Wp][4]
     if (Cin != 4) throw std::runtime_error("conv_wgrad: the pair-packed layout needs a 4-channel input");
-    conv_wgrad_g(make_geom_pair(B, H, W, Cout, KS), dy, x, out, splits, ldo, tile & 15, stream);
+    conv_wgrad_g(make_geom_pair(B, H, W, Cout, KS), dy, x, out, splits, ldo, tile & 15, stream, side);
     return;
   }
-  conv_wgrad_g(make_geom(B, H, W, Cin, Cout, KS), dy, x, out, splits, ldo, tile, stream);
+  conv_wgrad_g(make_geom(B, H, W, Cin, Cout, KS), dy, x, out, splits, ldo, tile, stream, side);
 }
 
 // out: fp32 [splits][Cout][ldo] weight-gradient slabs of a generalised-geometry

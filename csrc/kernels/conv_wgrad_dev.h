@@ -23,7 +23,7 @@ template <int BM, int BN, int STAGES, int WM = 2, int WN = 2, int BK_ = 64>
 __global__ void __launch_bounds__(64 * WM * WN) conv_wgrad_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
                                                          float* __restrict__ out, const ConvGeom g, int m_per_split,
                                                          int ldo, const SgdJob side = SgdJob{}) {
-  // side job (set_conv_side_sgd, as conv_fwd_kernel): the last side.nblk
+  // side job (dl_ops.h SideJob, as conv_fwd_kernel): the last side.nblk
   // workgroups run part of the step's SGD update beside the weight gradient
   const int wg_grid = (int)gridDim.x - side.nblk;
   if ((int)blockIdx.x >= wg_grid) {

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "dl_common.h"
+#include "dl_ops.h"
 #include "prep_dev.h"
 #include "sgd_dev.h"
 
@@ -269,51 +270,39 @@ void sgd_update(uintptr_t p, uintptr_t g, uintptr_t mom, uintptr_t p16, uintptr_
   DL_HIP_CHECK(hipGetLastError());
 }
 
-// size the update grid to the elements left after a skipped suffix (A/B)
-static bool g_sgd_trim = true;
-void set_sgd_trim(bool on) { g_sgd_trim = on; }
-
-// One-shot: the next sgd_update_slabs launch also prepares the next step
-// (prep_dev.h jobs + the first layer's packed weights from its tail range).
-static PrepArgs g_next_prep{};
-static bool g_next_armed = false;
-static bf16_t* g_next_pack = nullptr;
-static int g_next_pack_cp = 0;
-static int64_t g_next_pack_off = 0, g_next_pack_len = 0;  // the first layer's elements in the updated buffer
-
-// pack_off / pack_len: the first conv layer's weight [Cout][taps][C] as an
-// element range of the buffer the consuming update writes -- packed from the
-// main loop when the layer is not the update's slab tail (its gradient was
-// all-reduced at N > 1, so the update reads it from the flat gradient).
-void arm_sgd_next_prep(uintptr_t img, uintptr_t order, uintptr_t lab_all, uintptr_t lab_out, uintptr_t ctr,
-                       int n_order, int B, int C, std::vector<float> mean, std::vector<float> stdv, uintptr_t xp,
-                       int Cp, int H, int W, int sp, std::vector<uintptr_t> zp, std::vector<int64_t> zn,
-                       uintptr_t w1p, int w1_cp, int64_t pack_off, int64_t pack_len) {
-  if (g_next_armed) throw std::runtime_error("arm_sgd_next_prep: already armed (no sgd_update_slabs consumed it)");
-  if (!xp || !w1p || (w1_cp > 0 ? w1_cp < C : C > 4)) throw std::runtime_error("arm_sgd_next_prep: input buffer / packed weights");
-  if (pack_off % 4 || pack_len % 4 || pack_off < 0 || pack_len <= 0 || pack_len % C)
-    throw std::runtime_error("arm_sgd_next_prep: the first layer's element range must be 16-byte aligned");
+// The prep_dev.h jobs (gather + pad, zero) of a next-step preparation, with every check on it.
+static PrepArgs next_prep_args(const NextPrep& n) {
+  if (!n.xp || !n.w1p || n.C < 1 || (n.w1_cp > 0 ? n.w1_cp < n.C : n.C > 4))
+    throw std::runtime_error("next_prep: input buffer / packed weights");
+  if (n.pack_off % 4 || n.pack_len % 4 || n.pack_off < 0 || n.pack_len <= 0 || n.pack_len % n.C)
+    throw std::runtime_error("next_prep: the first layer's element range must be 16-byte aligned");
   PrepArgs a{};
-  a.xp = (bf16_t*)xp; a.C = C; a.Cp = Cp; a.H = H; a.W = W; a.sp = sp;
-  prep_set_gather(a, img, order, lab_all, lab_out, ctr, n_order, B, C, mean, stdv);
-  prep_set_pad(a, (int64_t)B * H * W);
-  prep_set_zero(a, zp, zn);
-  g_next_prep = a;
-  g_next_pack = (bf16_t*)w1p;
-  g_next_pack_cp = w1_cp;
-  g_next_pack_off = pack_off;
-  g_next_pack_len = pack_len;
-  g_next_armed = true;
+  a.xp = (bf16_t*)n.xp; a.C = n.C; a.Cp = n.Cp; a.H = n.H; a.W = n.W; a.sp = n.sp;
+  prep_set_gather(a, n.img, n.order, n.lab_all, n.lab_out, n.ctr, n.n_order, n.B, n.C, n.mean, n.stdv);
+  prep_set_pad(a, (int64_t)n.B * n.H * n.W);
+  prep_set_zero(a, n.zp, n.zn);
+  return a;
 }
 
-bool sgd_next_prep_armed() { return g_next_armed; }
-
-void disarm_sgd_next_prep() { g_next_armed = false; }
+// pack_off / pack_len: the first conv layer's weight [Cout][taps][C] as an
+// element range of the buffer the update writes -- packed from the main loop
+// when the layer is not the update's slab tail (its gradient was all-reduced
+// at N > 1, so the update reads it from the flat gradient).
+NextPrep next_prep(uintptr_t img, uintptr_t order, uintptr_t lab_all, uintptr_t lab_out, uintptr_t ctr, int n_order,
+                   int B, int C, std::vector<float> mean, std::vector<float> stdv, uintptr_t xp, int Cp, int H, int W,
+                   int sp, std::vector<uintptr_t> zp, std::vector<int64_t> zn, uintptr_t w1p, int w1_cp,
+                   int64_t pack_off, int64_t pack_len) {
+  const NextPrep n{img, order, lab_all, lab_out, ctr, n_order, B,   C,     mean,     stdv,    xp,
+                   Cp,  H,     W,       sp,      zp,  zn,      w1p, w1_cp, pack_off, pack_len};
+  next_prep_args(n);
+  return n;
+}
 
 void sgd_update_slabs(uintptr_t p, uintptr_t g, uintptr_t mom, uintptr_t p16, uintptr_t slot, float lr,
                       float momentum, float wd, int64_t n, std::vector<int64_t> offs, std::vector<int64_t> lens,
                       std::vector<uintptr_t> slabs, std::vector<int> splits, std::vector<int64_t> tail,
-                      uintptr_t tail_slab, int64_t skip_lo, int64_t skip_hi, uintptr_t stream, uintptr_t lr_dev) {
+                      uintptr_t tail_slab, int64_t skip_lo, int64_t skip_hi, uintptr_t stream, uintptr_t lr_dev,
+                      const NextPrep* next) {
   check_vec4(n, "sgd_update_slabs");
   SgdJob job = make_sgd_job(p, g, mom, p16, slot, lr, momentum, wd, 0, n, offs, lens, slabs, splits, tail, tail_slab,
                             lr_dev);
@@ -321,21 +310,19 @@ void sgd_update_slabs(uintptr_t p, uintptr_t g, uintptr_t mom, uintptr_t p16, ui
     if (skip_lo % 4 || skip_hi % 4 || skip_lo < 0 || skip_hi > n) throw std::runtime_error("sgd_update_slabs: bad skip");
     job.skip_lo4 = skip_lo / 4;
     job.skip_hi4 = skip_hi / 4;
-    if (skip_hi == n && g_sgd_trim) {
-      // a skipped suffix (the side job's range): the grid covers only the rest
-      // (the tail blocks cover their own range)
-      job.hi4 = std::max(job.lo4, job.skip_lo4);
-    }
+    // a skipped suffix (the side job's range): the grid covers only the rest
+    // (the tail blocks cover their own range)
+    if (skip_hi == n) job.hi4 = std::max(job.lo4, job.skip_lo4);
   }
   const int64_t n4 = n / 4;
-  PrepArgs next{};
-  if (g_next_armed) {
-    g_next_armed = false;
+  PrepArgs prep{};
+  if (next) {
+    prep = next_prep_args(*next);
     if (job.r.tail_nblk > 0) {  // the first layer is the slab tail: its blocks write the packed operand
-      if (job.r.tail_c != g_next_prep.C || job.r.tail_lo != g_next_pack_off)
+      if (job.r.tail_c != next->C || job.r.tail_lo != next->pack_off)
         throw std::runtime_error("sgd_update_slabs: the slab tail is not the first layer the next step packs");
     } else {  // the main loop packs the first layer's range
-      const int64_t lo4 = g_next_pack_off / 4, hi4 = (g_next_pack_off + g_next_pack_len) / 4;
+      const int64_t lo4 = next->pack_off / 4, hi4 = (next->pack_off + next->pack_len) / 4;
       if (lo4 < job.lo4 || hi4 > job.hi4 || (lo4 < job.skip_hi4 && job.skip_lo4 < hi4))
         throw std::runtime_error("sgd_update_slabs: the first layer is not updated by this launch's main loop");
       for (int k = 0; k < job.r.n; ++k)
@@ -343,19 +330,18 @@ void sgd_update_slabs(uintptr_t p, uintptr_t g, uintptr_t mom, uintptr_t p16, ui
           throw std::runtime_error("sgd_update_slabs: the first layer overlaps a slab range");
       job.pack_lo4 = lo4;
       job.pack_hi4 = hi4;
-      job.pack_c = g_next_prep.C;
+      job.pack_c = next->C;
     }
-    next = g_next_prep;
-    job.tail_pack = g_next_pack;
-    job.tail_pack_cp = g_next_pack_cp;
+    job.tail_pack = (bf16_t*)next->w1p;
+    job.tail_pack_cp = next->w1_cp;
   }
   if (n4 == 0) return;
-  dim3 grid(stream_grid(job.hi4 - job.lo4) + job.r.tail_nblk + next.nb_pad + next.nb_zero), block(256);
+  dim3 grid(stream_grid(job.hi4 - job.lo4) + job.r.tail_nblk + prep.nb_pad + prep.nb_zero), block(256);
   auto s = as_stream(stream);
-  if (mom && p16) sgd_slabs_kernel<true, true><<<grid, block, 0, s>>>(job, next);
-  else if (mom) sgd_slabs_kernel<true, false><<<grid, block, 0, s>>>(job, next);
-  else if (p16) sgd_slabs_kernel<false, true><<<grid, block, 0, s>>>(job, next);
-  else sgd_slabs_kernel<false, false><<<grid, block, 0, s>>>(job, next);
+  if (mom && p16) sgd_slabs_kernel<true, true><<<grid, block, 0, s>>>(job, prep);
+  else if (mom) sgd_slabs_kernel<true, false><<<grid, block, 0, s>>>(job, prep);
+  else if (p16) sgd_slabs_kernel<false, true><<<grid, block, 0, s>>>(job, prep);
+  else sgd_slabs_kernel<false, false><<<grid, block, 0, s>>>(job, prep);
   DL_HIP_CHECK(hipGetLastError());
 }
 

@@ -372,7 +372,7 @@ inline SgdJob make_reduce_job(uintptr_t g, int64_t lo, int64_t hi, const std::ve
 
 // A side job run by workgroup `bid` of the job's nblk extra workgroups of a
 // host launch (conv_fwd_kernel): no tail range, always a bf16 shadow (the
-// conv executors' flat buffers have one; make_side_job checks), momentum at
+// conv executors' flat buffers have one; side_sgd_job checks), momentum at
 // run time -- or a reduce-only job (red).
 __device__ __forceinline__ void sgd_side_block(const SgdJob& j, int bid) {
   if (j.red) slab_reduce_range_loop(j, bid, j.nblk);

@@ -1142,10 +1142,10 @@ def test_conv_fwd_per_call_options_leave_process_settings(C):
         C.set_conv_stages(3, 0)
 
 
-def test_conv_fwd_failed_call_disarms_side_job(C):
-    """A conv_fwd that throws in host validation (tile id 7, nothing launched)
-    takes the armed side job with it: the next streaming conv_fwd does not run
-    the update."""
+def test_conv_fwd_failed_call_side_job_is_not_run_later(C):
+    """A side job belongs to the call it is passed to: when that conv_fwd throws
+    in host validation (tile id 7, nothing launched), the next streaming
+    conv_fwd does not run the update."""
     dev = torch.device("cuda")
     n = 1024
     p = torch.randn(n, device=dev, generator=torch.Generator(device=dev).manual_seed(43))
@@ -1158,14 +1158,98 @@ def test_conv_fwd_failed_call_disarms_side_job(C):
     xp = _pad(x)
     C.set_conv_region(0)
     try:
-        C.set_conv_side_sgd(p.data_ptr(), grad.data_ptr(), 0, p16.data_ptr(), slot.data_ptr(), 0.1, 0.0, 0.0, 0, n, [],
-                            [], [], [], 0, 0)
+        job = C.side_sgd_job(p.data_ptr(), grad.data_ptr(), 0, p16.data_ptr(), slot.data_ptr(), 0.1, 0.0, 0.0, 0, n, [],
+                             [], [], [], 0, 0)
         y = torch.empty(B, H, H, cout, dtype=torch.bfloat16, device=dev)
         with pytest.raises(RuntimeError, match="bad tile id"):
-            C.conv_fwd(xp.data_ptr(), w.data_ptr(), y.data_ptr(), 0, 0, B, H, H, cin, cout, 5, 7, 1, _s())
+            C.conv_fwd(xp.data_ptr(), w.data_ptr(), y.data_ptr(), 0, 0, B, H, H, cin, cout, 5, 7, 1, _s(), side=job)
         y1, _ = _conv5(C, xp, w, tile, B, H, cin, cout, stats=False)
         assert torch.equal(p, p0) and torch.equal(p16, p16_0)
         y2, _ = _conv5(C, xp, w, tile, B, H, cin, cout, stats=False)
         assert torch.equal(y1, y2)
     finally:
         C.set_conv_region(1)
+
+
+# the side job of test_lr_device_gpu.py's conv_fwd case: a ragged range of a
+# 3084-float buffer with one in-place 5-split slab range
+_SIDE_N, _SIDE_LO, _SIDE_HI, _SIDE_OFF, _SIDE_LEN = 4 * 257 * 3, 4 * 100, 4 * 700, 4 * 300, 256
+
+
+@pytest.mark.parametrize("mom", [False, True])
+def test_conv_wgrad_carries_sgd_side_job(C, mom):
+    """conv_wgrad given an SGD side job directly (``side=``): the weight-gradient
+    slabs are bitwise those of the same call without a job, [lo, hi) of p / mom /
+    the bf16 shadow is bitwise sgd_update_ of that range with the same slabs, and
+    nothing outside [lo, hi) is touched."""
+    from torch_distlearn_amd.ops.flat import sgd_update_
+
+    dev = torch.device("cuda")
+    B, H, cin, cout, tile, splits = 2, 8, 64, 64, 1, 2
+    n, lo, hi, off, ln = _SIDE_N, _SIDE_LO, _SIDE_HI, _SIDE_OFF, _SIDE_LEN
+    K = 25 * cin
+    g0 = torch.Generator(device=dev).manual_seed(53)
+    xp = _pad(torch.randn(B, H, H, cin, device=dev, generator=g0).to(torch.bfloat16))
+    dyp = _pad(torch.randn(B, H, H, cout, device=dev, generator=g0).to(torch.bfloat16))
+    p = torch.randn(n, device=dev, generator=g0)
+    grad = torch.randn(n, device=dev, generator=g0)
+    m = torch.randn(n, device=dev, generator=g0) if mom else None
+    p16 = p.to(torch.bfloat16)
+    slab = torch.randn(5 * ln, device=dev, generator=g0)
+    slot = torch.tensor([3.0], device=dev)
+    lr, mu, wd = 0.0123, 0.9, 1e-4
+    p0, m0, p16_0 = p.clone(), None if m is None else m.clone(), p16.clone()
+
+    def wgrad(side):
+        out = torch.full((splits, cout, K), float("nan"), device=dev)
+        C.conv_wgrad(dyp.data_ptr(), xp.data_ptr(), out.data_ptr(), B, H, H, cin, cout, 5, splits, K, tile, 0, _s(),
+                     side=side)
+        torch.cuda.synchronize()
+        return out
+
+    plain = wgrad(None)
+    assert torch.equal(p, p0) and torch.equal(p16, p16_0)
+    job = C.side_sgd_job(p.data_ptr(), grad.data_ptr(), 0 if m is None else m.data_ptr(), p16.data_ptr(),
+                         slot.data_ptr(), lr, mu, wd, lo, hi, [off], [ln], [slab.data_ptr()], [5], 0)
+    carried = wgrad(job)
+    assert torch.isfinite(plain).all() and torch.equal(plain, carried)
+    # the reference: the stand-alone update of the range, same slabs
+    pr, mr, shr = p0.clone(), None if m0 is None else m0.clone(), p16_0.clone()
+    sgd_update_(pr[lo:hi], grad[lo:hi], lr, slot=slot, mom=None if mr is None else mr[lo:hi], momentum=mu,
+                weight_decay=wd, shadow=shr[lo:hi], slabs=[(off - lo, ln, slab, 5)])
+    torch.cuda.synchronize()
+    assert not torch.equal(pr[lo:hi], p0[lo:hi])
+    for got, want, before in ((p, pr, p0), (m, mr, m0), (p16, shr, p16_0)):
+        if got is None:
+            continue
+        assert torch.equal(got[lo:hi], want[lo:hi])
+        assert torch.equal(got[:lo], before[:lo]) and torch.equal(got[hi:], before[hi:])
+
+
+def test_conv_fwd_side_job_on_region_kernel_raises_before_launch(C):
+    """A side job on a call that takes the region kernel fails in host
+    validation, before anything is enqueued: y keeps its sentinel and p is
+    untouched."""
+    from torch_distlearn_amd.ops.conv import pack_tile
+
+    dev = torch.device("cuda")
+    B, H, cin, cout, tile = 2, 16, 64, 64, 2
+    n = 1024
+    p = torch.randn(n, device=dev, generator=torch.Generator(device=dev).manual_seed(59))
+    p16 = p.to(torch.bfloat16)
+    grad = torch.ones(n, device=dev)
+    slot = torch.ones(1, device=dev)
+    p0, p16_0 = p.clone(), p16.clone()
+    x, w = _conv5_operands(B, H, cin, cout, 61)
+    xp = _pad(x)
+    C.set_conv_region(1)
+    assert C.conv_region_ok(B, H, H, cin, cout, 5, tile, 1) == 1
+    y = torch.full((B, H, H, cout), -7.0, dtype=torch.bfloat16, device=dev)
+    job = C.side_sgd_job(p.data_ptr(), grad.data_ptr(), 0, p16.data_ptr(), slot.data_ptr(), 0.1, 0.0, 0.0, 0, n, [], [],
+                         [], [], 0)
+    with pytest.raises(RuntimeError, match="side job"):
+        C.conv_fwd(xp.data_ptr(), w.data_ptr(), y.data_ptr(), 0, 0, B, H, H, cin, cout, 5, pack_tile(tile), 1, _s(),
+                   side=job)
+    torch.cuda.synchronize()
+    assert bool((y == -7.0).all())
+    assert torch.equal(p, p0) and torch.equal(p16, p16_0)

@@ -552,7 +552,7 @@ def test_deferred_slab_reduce_is_bitwise(dev, monkeypatch, momentum):
     the first layer's weight-gradient launch -- still bitwise the same; and with
     the update launch preparing the next step of the unrolled graph (its
     batch gathered, accumulators zeroed, first-layer operand packed: the
-    executor's arm_next_prep) -- still bitwise, across an epoch boundary."""
+    executor's next_prep) -- still bitwise, across an epoch boundary."""
     from torch_distlearn_amd import Tree
     from torch_distlearn_amd.data import DeviceLoader, PartitionedDataset, synthetic_cifar10
     from torch_distlearn_amd.engine import DataParallelTrainer
@@ -588,7 +588,8 @@ def test_deferred_slab_reduce_is_bitwise(dev, monkeypatch, momentum):
         tr.run(ld, 11, unroll=4)  # 8 steps per epoch: graphs of 4, 2, 1 steps, then a new epoch
         torch.cuda.synchronize()
         assert (tr.executor.prepared_ahead > 0) == (nxt == "1")
-        assert not tr.executor.C.sgd_next_prep_armed()
+        assert not tr.executor._prepared  # no step is left marked as prepared
+        assert not hasattr(tr.executor.C, "arm_sgd_next_prep")
         outs.append(tr.flat.data.clone())
     assert all(torch.equal(outs[0], o) for o in outs[1:])
 
@@ -659,7 +660,8 @@ def test_multinode_fused_reduce_is_bitwise(dev, monkeypatch, momentum):
         tr.run(ld, 11, unroll=4)
         torch.cuda.synchronize()
         assert (tr.executor.prepared_ahead > 0) == (nxt == "1")
-        assert not tr.executor.C.sgd_next_prep_armed()
+        assert not tr.executor._prepared  # no step is left marked as prepared
+        assert not hasattr(tr.executor.C, "arm_sgd_next_prep")
         outs.append(tr.flat.data.clone())
     assert all(torch.equal(outs[0], o) for o in outs[1:])
 

@@ -197,7 +197,7 @@ def test_device_rate_slabs_is_bitwise_immediate(dev, rate, n, kind, mom, count):
 @pytest.mark.parametrize("mom", [False, True])
 def test_side_job_device_rate_is_bitwise_immediate(dev, rate, mom):
     """A streaming conv_fwd launch carrying the update of elements [lo, hi) as
-    extra workgroups (set_conv_side_sgd), armed with lr_dev and with the
+    extra workgroups (side_sgd_job), built with lr_dev and with the
     immediate value: the updated range is bitwise equal (and so is the conv).
     Shape: the smallest of test_convnet_gpu.py's streaming shapes."""
     from torch_distlearn_amd import _native
@@ -219,9 +219,10 @@ def test_side_job_device_rate_is_bitwise_immediate(dev, rate, mom):
         y = torch.empty(B, H, H, cout, dtype=torch.bfloat16, device=dev)
         C.set_conv_region(0)  # the streaming kernel hosts side jobs
         try:
-            C.set_conv_side_sgd(p.data_ptr(), g.data_ptr(), 0 if m is None else m.data_ptr(), sh.data_ptr(),
-                                slot.data_ptr(), imm, MU, WD, lo, hi, [off], [ln], [slab.data_ptr()], [5], 0, ptr)
-            C.conv_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), 0, 0, B, H, H, cin, cout, 5, tile, 1, _s())
+            job = C.side_sgd_job(p.data_ptr(), g.data_ptr(), 0 if m is None else m.data_ptr(), sh.data_ptr(),
+                                 slot.data_ptr(), imm, MU, WD, lo, hi, [off], [ln], [slab.data_ptr()], [5], 0, ptr)
+            C.conv_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), 0, 0, B, H, H, cin, cout, 5, tile, 1, _s(),
+                       side=job)
         finally:
             C.set_conv_region(1)
         torch.cuda.synchronize()

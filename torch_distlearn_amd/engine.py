@@ -330,7 +330,7 @@ class DataParallelTrainer:
         the local SGD step only when ``local`` -- a step that syncs with the
         server runs its update after the sync, EASGD_client.lua:106-117).
         ``prep_next``: another step on the same DeviceLoader follows in the
-        same graph; the update launch prepares it (executor arm_next_prep)."""
+        same graph; the update launch prepares it (executor next_prep)."""
         f = self.flat
         # zero grads, participation slot = 1 (this node contributes this round);
         # a native executor that overwrites every gradient sets the slot itself
@@ -341,38 +341,35 @@ class DataParallelTrainer:
             labels = x.labels_out if hasattr(x, "gather_args") else y
             for h in self.step_hooks:
                 h(self.last_logits(), labels)
-        armed = False
-        if prep_next and self._update_preps_next() and os.environ.get("DISTLEARN_PREP_NEXT", "1") == "1":
-            arm = getattr(self.executor, "arm_next_prep", None)
-            armed = bool(arm(x)) if arm is not None else False
-        try:
-            if self.algo == "sgd":
-                self.sgd.step(f, self._lr_arg(), momentum=self.momentum, weight_decay=self.weight_decay,
-                              momentum_buf=self.mom, slabs=self._slabs, skip=self._side)
-            elif self.algo == "ea" or (self.algo == "async" and local):
-                self._local_update()
-        except BaseException:
-            if armed:  # the update never consumed the next-step preparation
-                self.executor.C.disarm_sgd_next_prep()
-                self.executor._prefetched = False
-            raise
+        updates = self.algo in ("sgd", "ea") or (self.algo == "async" and local)
+        nxt = None
+        if (prep_next and updates and self._update_preps_next()
+                and os.environ.get("DISTLEARN_PREP_NEXT", "1") == "1" and hasattr(self.executor, "next_prep")):
+            nxt = self.executor.next_prep(x)
+        if self.algo == "sgd":
+            self.sgd.step(f, self._lr_arg(), momentum=self.momentum, weight_decay=self.weight_decay,
+                          momentum_buf=self.mom, slabs=self._slabs, skip=self._side, next_prep=nxt)
+        elif updates:
+            self._local_update(nxt)
+        if nxt is not None:
+            self.executor.mark_prepared()  # its launch is enqueued: the next step skips its prep
         return loss
 
     def _update_preps_next(self) -> bool:
         """Whether the step's final update is ONE fused fp32 SGD launch that can
-        also prepare the next step of an unrolled graph (flat_sgd_ consumes an
-        armed arm_next_prep): not per-bucket updates, not the bf16 gradient
-        wire (its update reads the bf16 copy).  An AsyncEA client's local-step
-        updates inside its unrolled graph consume the preparation too; a
-        syncing step (update after syncClient, outside the graph) never arms it."""
+        also prepare the next step of an unrolled graph (flat_sgd_
+        ``next_prep``): not per-bucket updates, not the bf16 gradient wire
+        (its update reads the bf16 copy).  An AsyncEA client's local-step
+        updates inside its unrolled graph carry the preparation too; a
+        syncing step (update after syncClient, outside the graph) never does."""
         return (self.algo in ("sgd", "ea", "async") and not self.bucket_updates and self.grad_comm_dtype == "fp32"
                 and (self._slabs is not None or self.reduces_grads or self.algo != "sgd"))
 
-    def _local_update(self) -> None:
+    def _local_update(self, next_prep=None) -> None:
         from .ops.flat import flat_sgd_
 
         flat_sgd_(self.flat, self._lr_arg(), slot=None, mom=self.mom, momentum=self.momentum,
-                  weight_decay=self.weight_decay, slabs=self._slabs, skip=self._side)
+                  weight_decay=self.weight_decay, slabs=self._slabs, skip=self._side, next_prep=next_prep)
 
     def step(self, x, y: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One training step on this node's mini-batch; returns the loss

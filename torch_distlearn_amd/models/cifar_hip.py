@@ -247,8 +247,8 @@ class CifarHIPExecutor:
         # by one reduce-only launch after the last weight gradient
         self._ride: dict = {}
         self._merged: tuple = ()
-        self._prefetched = False  # the coming step was prepared by the last update launch (arm_next_prep)
-        self.prepared_ahead = 0   # steps armed that way (counted at capture)
+        self._prepared = False   # the coming step was prepared by the last update launch (next_prep)
+        self.prepared_ahead = 0  # steps prepared that way (counted at capture)
         self._side = None    # side SGD carried by a dgrad launch (side_update)
 
     # ------------------------------------------------------------------ buffers
@@ -466,17 +466,12 @@ class CifarHIPExecutor:
             ctr = x.ctr.data_ptr()  # advanced by head_wgrad after the gather read it
         if labels.dtype != torch.int64:
             raise ValueError("labels must be int64")
-        if self._prefetched:  # the previous step's update launch prepared this one (arm_next_prep)
-            self._prefetched = False
-            if self.C.sgd_next_prep_armed():
-                self.C.disarm_sgd_next_prep()
-                raise RuntimeError("arm_next_prep: no update launch consumed the next-step preparation")
+        if self._prepared:  # the previous step's update launch prepared this one (next_prep)
+            self._prepared = False
             if not hasattr(x, "gather_args"):
-                raise RuntimeError("arm_next_prep: the prepared step must run on the same DeviceLoader")
+                raise RuntimeError("next_prep: the prepared step must run on the same DeviceLoader")
             B = x.batch
         else:
-            if self.C.sgd_next_prep_armed():  # stale (an update that raised after arm_next_prep): drop it
-                self.C.disarm_sgd_next_prep()
             B = self._prep(x, s, with_transposes=not self.head_transposes)
         self._last_b = B
         self._forward(B, s, train=True, pool_last=not self.head_pool)
@@ -564,14 +559,16 @@ class CifarHIPExecutor:
             tile, splits, direct = self.wplan[i]
             wtile = pack_tile(tile, pair=i == 0 and self.pair1)  # pair-packed layer 1 (csrc make_geom_pair)
             gw = self.g32[self._leaf(i, 0)]
+            side = None
             if i == 0 and self._side is not None and self._side["w"] is not None:
-                self._arm_side(self._side["w"])  # this launch also updates blocks 1 .. side block - 1
+                side = self._side_job(self._side["w"])  # this launch also updates blocks 1 .. side block - 1
             if direct:
-                C.conv_wgrad(dY.data_ptr(), xin.data_ptr(), gw.data_ptr(), B, h, h, kcin, cout, KSIZE, 1, K, wtile, 0, s)
+                C.conv_wgrad(dY.data_ptr(), xin.data_ptr(), gw.data_ptr(), B, h, h, kcin, cout, KSIZE, 1, K, wtile, 0, s,
+                             side=side)
             else:
                 slab = self.wslab_l[i]
                 C.conv_wgrad(dY.data_ptr(), xin.data_ptr(), slab.data_ptr(), B, h, h, kcin, cout, KSIZE, splits, K,
-                             wtile, 0, s)
+                             wtile, 0, s, side=side)
                 if i in self._deferred:
                     pass  # summed by the update kernel (defer_slab_reduce)
                 elif i in self._ride:
@@ -601,20 +598,19 @@ class CifarHIPExecutor:
                                                   h, h, cout, cin, KSIZE, dt, self.y[i - 1].data_ptr(),
                                                   self.coef[i - 1].data_ptr(), prt.data_ptr(), s)
                 else:
+                    side = self._ride.get(i)  # this launch also sums this block's weight-gradient slabs ...
                     if self._side is not None and i == self._side["block"]:
-                        self._arm_side()  # this launch also runs the update of blocks >= i
-                    elif i in self._ride:
-                        C.set_conv_side_reduce(*self._ride[i])  # ... or sums this block's weight-gradient slabs
+                        side = self._side_job(self._side)  # ... or runs the update of blocks >= i
                     if fix:
                         # split-K slices combined inside the launch, whose reducers also
                         # run block i-1's BN backward reduce (no combine_bwd_reduce launch)
                         dp_reduced = C.conv_fwd_fix(dY.data_ptr(), self.wt[i].data_ptr(), self.dP[i - 1].data_ptr(),
                                                     0, self.slabs.data_ptr(), B, h, h, cout, cin, KSIZE, dt, ds,
                                                     self.y[i - 1].data_ptr(), self.coef[i - 1].data_ptr(),
-                                                    prt.data_ptr(), s)
+                                                    prt.data_ptr(), s, side=side)
                     else:
                         C.conv_fwd(dY.data_ptr(), self.wt[i].data_ptr(), self.dP[i - 1].data_ptr(), 0,
-                                   self.slabs.data_ptr(), B, h, h, cout, cin, KSIZE, dt, ds, s)
+                                   self.slabs.data_ptr(), B, h, h, cout, cin, KSIZE, dt, ds, s, side=side)
                     if i in self._ride:
                         for j in range(4):
                             self._ready(self._leaf(i, j))
@@ -657,7 +653,7 @@ class CifarHIPExecutor:
         weight to the end of the flat buffer (blocks >= block, the
         classifier) inside that block's dgrad launch, as extra workgroups on
         the CUs its one-workgroup-per-CU grid leaves free (csrc
-        set_conv_side_sgd): their gradients are final by then (weight
+        side_sgd_job): their gradients are final by then (weight
         gradients in the flat buffer or, deferred, in their slabs) and nothing
         later in the step reads them.  One node only (after
         :meth:`defer_slab_reduce`).  Returns the flat element range [lo, hi)
@@ -718,7 +714,7 @@ class CifarHIPExecutor:
         (the one-node update sums them itself instead: defer_slab_reduce).
         Rather than one slab_reduce launch per layer, a layer whose dgrad is a
         streaming launch has its slabs summed by extra workgroups of that
-        dgrad (csrc set_conv_side_reduce, on the CUs its grid leaves free),
+        dgrad (csrc side_reduce_job, on the CUs its grid leaves free),
         and the other layers are summed together by ONE reduce-only launch
         after the last of their weight gradients (slab_reduce_multi: up to 4
         unpadded ranges + the first layer's channel-padded 128-way slabs).
@@ -737,8 +733,8 @@ class CifarHIPExecutor:
         for i in ride:
             lf = self._leaf(i, 0)
             off, n = f.offsets[lf], f.numels[lf]
-            self._ride[i] = (f.grad.data_ptr(), off, off + n, [off], [n], [self.wslab_l[i].data_ptr()],
-                             [self.wplan[i][1]], 0)
+            self._ride[i] = self.C.side_reduce_job(f.grad.data_ptr(), off, off + n, [off], [n],
+                                                   [self.wslab_l[i].data_ptr()], [self.wplan[i][1]], 0)
         merged = sorted(inplace + padded)
         if merged:
             lfs = {i: self._leaf(i, 0) for i in merged}
@@ -757,15 +753,15 @@ class CifarHIPExecutor:
     def _reduce_merged(self, s: int) -> None:
         self.C.slab_reduce_multi(*self._merged_args, s)
 
-    def _arm_side(self, job: Optional[dict] = None) -> None:
+    def _side_job(self, job: dict):
+        """The SideJob of this call's launch: the update of ``job``'s range at the current rate."""
         sd = self._side
-        job = job or sd
         p, g, mom, p16, slot = sd["args"]
         mo, wd = sd["mw"]
         lo, hi = job["range"]
         lr, lr_dev = _lr_args(sd["lr"](), True)  # a tensor rate: the side job reads it on the device
-        self.C.set_conv_side_sgd(p, g, mom, p16, slot, lr, mo, wd, lo, hi, *job["slabs"],
-                                 0, lr_dev)  # 0: one float4 per thread over the range
+        return self.C.side_sgd_job(p, g, mom, p16, slot, lr, mo, wd, lo, hi, *job["slabs"],
+                                   0, lr_dev)  # 0: one float4 per thread over the range
 
     def defer_slab_reduce(self):
         """Leave every split-K weight gradient in its slabs: the slab_reduce
@@ -787,31 +783,32 @@ class CifarHIPExecutor:
         return [(self._leaf(i, 0), self.wslab_l[i], self.wplan[i][1], self.couts[i], taps, self._slab_cp(i),
                  self.cins_real[i]) for i in blocks]
 
-    def arm_next_prep(self, loader) -> bool:
-        """Let the coming update launch (flat_sgd_ with the deferred slabs)
-        prepare the NEXT step on ``loader`` in extra workgroups: gather +
-        normalise its batch into the layer-1 buffer, zero its accumulators,
-        and write the updated first-layer weights straight into their packed
-        operand (the update's tail range) -- so the next :meth:`forward_backward`
-        skips its prep launch.  For consecutive steps of an unrolled graph
-        (engine.py _capture_multi); the step counter the gather reads was
-        advanced by this step's head kernel.  False (nothing armed) when the
-        update cannot carry it: the first layer's slab reduce not deferred,
-        the dgrad transposes in the prep launch, no device loader."""
+    def next_prep(self, loader):
+        """The NextPrep with which the step's update launch (flat_sgd_
+        ``next_prep``) prepares the NEXT step on ``loader`` in extra
+        workgroups: gather + normalise its batch into the layer-1 buffer, zero
+        its accumulators, and write the updated first-layer weights straight
+        into their packed operand (the update's tail range).  For consecutive
+        steps of an unrolled graph (engine.py _capture_multi); the step counter
+        the gather reads was advanced by this step's head kernel.  None when
+        the update cannot carry it: the first layer's slab reduce not deferred,
+        the dgrad transposes in the prep launch, no device loader.  Changes no
+        state: the caller reports the enqueued launch with :meth:`mark_prepared`."""
         if (not hasattr(loader, "gather_args") or self.cins[0] == self.cins_real[0]
                 or not self.head_transposes or loader.batch > self.cap):
-            return False
+            return None
         h = self.hs[0]
         img, order, lab_all, lab_out, ctr, n_order, C, mean, std = loader.gather_args()
         if (loader.H, loader.W, C) != (h, h, self.cins_real[0]):
-            return False
+            return None
         lf = self._leaf(0, 0)
-        self.C.arm_sgd_next_prep(img, order, lab_all, lab_out, ctr, n_order, loader.batch, C, mean, std,
-                                 self.x8.data_ptr(), self.kin0, h, h, SPAD, *self._zero_args(True),
-                                 self.w1p.data_ptr(), self.w1_cp, self.flat.offsets[lf] - HEADER, self.flat.numels[lf])
-        self._prefetched = True
-        self.prepared_ahead += 1
-        return True
+        return self.C.next_prep(img, order, lab_all, lab_out, ctr, n_order, loader.batch, C, mean, std,
+                                self.x8.data_ptr(), self.kin0, h, h, SPAD, *self._zero_args(True),
+                                self.w1p.data_ptr(), self.w1_cp, self.flat.offsets[lf] - HEADER, self.flat.numels[lf])
+
+    def mark_prepared(self) -> None:
+        """An update launch carrying :meth:`next_prep` is enqueued: the next forward_backward skips its prep."""
+        self._prepared, self.prepared_ahead = True, self.prepared_ahead + 1
 
     def _region_dgrad(self, i: int, B: int) -> bool:
         """Whether block i's (unsplit) dgrad runs on the region (tap-reuse)

@@ -194,7 +194,7 @@ def _lr_args(lr, cuda: bool):
 
 def sgd_update_(p: torch.Tensor, g: torch.Tensor, lr, slot: torch.Tensor | None = None,
                 mom: torch.Tensor | None = None, momentum: float = 0.0, weight_decay: float = 0.0,
-                shadow: torch.Tensor | None = None, slabs=None, tail=None, skip=None) -> None:
+                shadow: torch.Tensor | None = None, slabs=None, tail=None, skip=None, next_prep=None) -> None:
     """p -= lr * (g/n + wd*p) [with momentum buffer]; n from ``slot`` (device).
     ``lr``: a float, or a 1-element fp32 CUDA tensor the kernel reads the rate
     from (bitwise the same update as that fp32 value passed as a float).
@@ -205,11 +205,10 @@ def sgd_update_(p: torch.Tensor, g: torch.Tensor, lr, slot: torch.Tensor | None 
     stand-alone reduce's sum).  ``tail``: one channel-padded range
     (offset, numel, slab tensor, splits, Cout, taps, Cp, C) reduced by extra
     blocks of the same launch.  ``skip``: elements [lo, hi) of p left alone
-    (updated inside the step by a conv launch's side job)."""
-    # an armed next-step preparation (executor arm_next_prep) rides the slab-capable launch
-    armed = p.is_cuda and native().sgd_next_prep_armed()
+    (updated inside the step by a conv launch's side job).  ``next_prep``: a
+    native NextPrep (executor next_prep) the launch also carries out."""
     lr, lr_dev = _lr_args(lr, p.is_cuda)
-    if slabs or tail is not None or skip is not None or armed:
+    if slabs or tail is not None or skip is not None or next_prep is not None:  # the slab-capable launch
         if not p.is_cuda or g.dtype != torch.float32:
             raise ValueError("sgd_update_: slab gradients / the next-step preparation need an fp32 gradient "
                              "on the GPU")
@@ -223,7 +222,7 @@ def sgd_update_(p: torch.Tensor, g: torch.Tensor, lr, slot: torch.Tensor | None 
                                   [int(n) for _, n, _, _ in slabs], [t.data_ptr() for _, _, t, _ in slabs],
                                   [int(k) for _, _, _, k in slabs], tl, tptr,
                                   int(skip[0]) if skip else 0, int(skip[1]) if skip else 0, stream_handle(),
-                                  lr_dev)
+                                  lr_dev, next_prep)
         return
     if p.is_cuda:
         fn = native().sgd_update_g16 if g.dtype == torch.bfloat16 else native().sgd_update
@@ -251,7 +250,7 @@ def _overlaps(x: torch.Tensor, y: torch.Tensor) -> bool:
 
 def flat_sgd_(flat: "FlatParams", lr, slot: torch.Tensor | None = None, mom: torch.Tensor | None = None,
               momentum: float = 0.0, weight_decay: float = 0.0, grad: torch.Tensor | None = None,
-              slabs=None, skip=None) -> None:
+              slabs=None, skip=None, next_prep=None) -> None:
     """The fused update over a FlatParams' parameter body: the 64-element
     header (whose gradient element is the participation count) is left out,
     so ``n`` never flows into the parameter buffer.  ``lr``: a float or a
@@ -262,7 +261,7 @@ def flat_sgd_(flat: "FlatParams", lr, slot: torch.Tensor | None = None, mom: tor
     :func:`sgd_update_`): unpadded ones (Cp == C) with < 32 splits are read
     in place, at most one other is reduced by extra blocks of the launch.
     ``skip``: a flat element range [lo, hi) (offsets into ``flat.data``)
-    already updated inside the step."""
+    already updated inside the step.  ``next_prep``: as :func:`sgd_update_`."""
     H = HEADER
     g = flat.grad if grad is None else grad
     rng, tail = None, None
@@ -282,7 +281,7 @@ def flat_sgd_(flat: "FlatParams", lr, slot: torch.Tensor | None = None, mom: tor
     sgd_update_(flat.data[H:], g[H:], lr, slot=slot, mom=None if mom is None else mom[H:],
                 momentum=momentum, weight_decay=weight_decay,
                 shadow=None if flat.shadow is None else flat.shadow[H:], slabs=rng, tail=tail,
-                skip=None if skip is None else (max(0, skip[0] - H), skip[1] - H))
+                skip=None if skip is None else (max(0, skip[0] - H), skip[1] - H), next_prep=next_prep)
 
 
 def lr_ring_set_(ring: torch.Tensor, offset: int, values) -> None:

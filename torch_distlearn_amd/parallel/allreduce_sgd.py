@@ -105,7 +105,7 @@ class AllReduceSGD:
 
     def step(self, flat: FlatParams, lr, momentum: float = 0.0, weight_decay: float = 0.0,
              momentum_buf: Optional[torch.Tensor] = None, already_reduced: bool = False, slabs=None,
-             skip=None) -> None:
+             skip=None, next_prep=None) -> None:
         """Fused ``sumAndNormalizeGradients`` + SGD update over a FlatParams:
         all-reduce (unless the bucketer already did), then ONE kernel
         ``p -= lr*(g/n + wd*p)`` (+momentum, + bf16 shadow refresh).  This is
@@ -115,11 +115,14 @@ class AllReduceSGD:
         only: nothing is all-reduced): leaves whose gradient the update sums
         from split-K slabs itself (ops/flat.py flat_sgd_); ``skip``: a flat
         element range [lo, hi) already updated inside the step (a conv
-        launch's side job)."""
+        launch's side job); ``next_prep``: a native NextPrep that the single
+        fused fp32 update launch also carries out (ops/flat.py flat_sgd_)."""
         if (slabs or skip) and self.tree.numNodes > 1:
             raise ValueError("AllReduceSGD.step: slab gradients are never all-reduced (one node only)")
         g = None
         bk = self.bucketer if (self.bucketer is not None and flat is self.bucketer.flat) else None
+        if next_prep is not None and bk is not None and not already_reduced and (bk.early is not None or bk.wire16):
+            raise ValueError("AllReduceSGD.step: per-bucket updates / the bf16 wire cannot carry next_prep")
         if not already_reduced:
             if bk is not None:
                 bk.finish(widen=False)  # bf16 wire: the update reads the reduced bf16 copy directly
@@ -132,7 +135,7 @@ class AllReduceSGD:
         if bk is not None and bk.wire16 and not already_reduced:
             g = flat.grad16
         flat_sgd_(flat, lr, slot=flat.slot, mom=momentum_buf, momentum=momentum, weight_decay=weight_decay, grad=g,
-                  slabs=slabs, skip=skip)
+                  slabs=slabs, skip=skip, next_prep=next_prep)
 
     def enable_bucket_updates(self, flat: FlatParams, lr_fn, momentum: float = 0.0, weight_decay: float = 0.0,
                               momentum_buf: Optional[torch.Tensor] = None) -> bool:
