@@ -6,13 +6,21 @@ products, two K slabs, one bf16 rounding), then mutated the way a kernel goes
 wrong: a border tap skipped at one pixel, a lost store lane, a wrong last row
 of the M tail, truncation instead of round-to-nearest-even, a split-K slab
 rounded through bf16, two output rows swapped.  Every mutation must raise under
-the oracle; the ratio of the old check is recorded for the ones it misses."""
+the oracle; the ratio of the old check is recorded for the ones it misses.
+
+The second half checks the BatchNorm + ReLU + pool and head oracles of
+tests/kernels/exact_bn_head.py against fp64 autograd, shows that the integer
+inputs tell the pool rule's wrong variants apart, and that a plain fp32
+evaluation of the kernels' formulas stays inside the derived bounds while a
+misrouted gradient or a dropped item does not."""
 import functools
 
 import pytest
 import torch
+import torch.nn.functional as F
 
 from tests.kernels import exact
+from tests.kernels import exact_bn_head as xb
 
 BF16 = torch.bfloat16
 SHAPES = [(8, 32, 8, 64), (8, 16, 64, 128), (3, 4, 256, 128)]  # (B, H, Cin, Cout), 5x5, pad 2
@@ -164,3 +172,173 @@ def test_stats_oracle():
     bad[3, 0] -= yf[3, -1].float()  # the last pixel missing from the sums
     with pytest.raises(AssertionError):
         exact.assert_stats(bad, y, 4)
+
+
+# ---------------------------------------------------------------------------
+# BatchNorm + ReLU + pool / head oracles (tests/kernels/exact_bn_head.py)
+# ---------------------------------------------------------------------------
+def _autograd_bn_relu_pool(y, gamma, beta, dP, eps):
+    """fp64 batch_norm -> relu -> max_pool2d and its gradients by autograd (NHWC in / out)."""
+    yr = y.double().permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+    g, b = gamma.double().clone().requires_grad_(True), beta.double().clone().requires_grad_(True)
+    o = F.max_pool2d(F.relu(F.batch_norm(yr, None, None, g, b, True, 0.0, eps)), 2, 2)
+    o.backward(dP.double().permute(0, 3, 1, 2))
+    return o.detach().permute(0, 2, 3, 1), yr.grad.permute(0, 2, 3, 1), g.grad, b.grad
+
+
+def test_bn_pool_references_match_autograd():
+    """On tie-free real data with the coefficients taken in fp64 the reference
+    formulas (forward, sums, apply) equal fp64 autograd to 1e-12 (relative to
+    the largest magnitude of each output)."""
+    B, H, C, eps = 3, 6, 16, 1e-3
+    g = torch.Generator().manual_seed(11)
+    y = torch.randn(B, H, H, C, generator=g, dtype=torch.float64) * 2 + 0.5
+    gamma = (torch.rand(C, generator=g, dtype=torch.float64) + 0.5) * torch.where(torch.arange(C) % 3 == 0, -1.0, 1.0)
+    beta = torch.randn(C, generator=g, dtype=torch.float64) * 0.1
+    dP = torch.randn(B, H // 2, H // 2, C, generator=g, dtype=torch.float64)
+    M = B * H * H
+    yf = y.reshape(-1, C)
+    mean = yf.mean(0)
+    invstd = ((yf * yf).mean(0) - mean * mean + eps).rsqrt()
+    coef = torch.stack([mean, invstd, gamma * invstd, beta - mean * gamma * invstd])
+    # fp64 coefficients: the fp32 rounding of z inside pool_select cannot change a tie-free choice
+    best, sel = xb.pool_select(y, coef[2], coef[3])
+    z = xb.windows(coef[2] * y + coef[3]).clamp_min(0)
+    assert int((z == z.max(3, keepdim=True).values).sum(3).max()) == 1 or bool((z.max(3).values == 0).any())
+    o, dy_ag, dg_ag, db_ag = _autograd_bn_relu_pool(y, gamma, beta, dP, eps)
+    pooled = z.max(3).values
+    assert float((pooled - o).abs().max()) <= 1e-12 * float(o.abs().max())
+    assert float((best - pooled).abs().max()) <= 2.0 ** -23 * float(pooled.abs().max())
+    s_dz, s_dzx, _, _ = xb.bwd_sums_ref(y, dP, coef)
+    assert float((s_dz - db_ag).abs().max()) <= 1e-12 * float(db_ag.abs().max())
+    assert float((s_dzx - dg_ag).abs().max()) <= 1e-12 * float(dg_ag.abs().max())
+    dy, _, _, _ = xb.apply_ref(y, dP, coef, gamma, s_dz, s_dzx, M)
+    assert float((dy - dy_ag).abs().max()) <= 1e-12 * float(dy_ag.abs().max())
+
+
+def test_bn_coefficients_match_torch_running_stats():
+    """bn_coefficients (train) equals fp64 F.batch_norm's running statistics
+    (unbiased variance) and normalisation; eval mode uses rmean - bias."""
+    g = torch.Generator().manual_seed(12)
+    B, H, C, eps, mom = 4, 4, 8, 1e-3, 0.1
+    y = torch.randn(B, H, H, C, generator=g, dtype=torch.float64) * 3 + 2
+    gamma, beta = torch.randn(C, generator=g, dtype=torch.float64), torch.randn(C, generator=g, dtype=torch.float64)
+    bias = torch.randn(C, generator=g, dtype=torch.float64)
+    rm, rv = torch.randn(C, generator=g, dtype=torch.float64), torch.rand(C, generator=g, dtype=torch.float64) + 0.5
+    yf = y.reshape(-1, C)
+    M = yf.shape[0]
+    sums = torch.stack([yf.sum(0), (yf * yf).sum(0)])
+    mom32, eps32 = float(torch.tensor(mom, dtype=torch.float32)), float(torch.tensor(eps, dtype=torch.float32))
+    r = xb.bn_coefficients(sums, M, gamma, beta, bias, eps, mom, (rm, rv), 0)
+    trm, trv = rm.clone(), rv.clone()
+    z = F.batch_norm((y + bias).permute(0, 3, 1, 2), trm, trv, gamma, beta, True, mom32, eps32).permute(0, 2, 3, 1)
+    torch.testing.assert_close(r["rmean"], trm, rtol=1e-12, atol=1e-12)
+    torch.testing.assert_close(r["rvar"], trv, rtol=1e-12, atol=1e-12)
+    torch.testing.assert_close(r["scale"] * y + r["shift"], z, rtol=1e-9, atol=1e-9)
+    e = xb.bn_coefficients(None, M, gamma, beta, bias, eps, mom, (rm, rv), 1)
+    z = F.batch_norm((y + bias).permute(0, 3, 1, 2), rm, rv, gamma, beta, False, mom32, eps32).permute(0, 2, 3, 1)
+    torch.testing.assert_close(e["scale"] * y + e["shift"], z, rtol=1e-9, atol=1e-9)
+    assert torch.equal(e["rmean"], rm) and torch.equal(e["rvar"], rv)
+
+
+def test_integer_inputs_tell_pool_rules_apart():
+    """On the exact regime's integer inputs a last-index tie-break and a >= 0
+    ReLU test both change dz (so every kernel copy of the rule is pinned), the
+    windows hold ties, positive ties and all-nonpositive windows in numbers,
+    and the regime's exactness checks pass; dy needs real bf16 roundings."""
+    B, H, C = 4, 8, 64
+    y, dP, coef, gamma = xb.int_bn_inputs(B, H, C, torch.Generator().manual_seed(1))
+    dz, _ = xb.bwd_terms(y, dP, coef, exact_regime=True)
+    dz_last, _ = xb.bwd_terms(y, dP, coef, tie="last")
+    dz_ge, _ = xb.bwd_terms(y, dP, coef, positive="ge")
+    assert int((dz != dz_last).sum()) > 100 and int((dz != dz_ge).sum()) > 100
+    best, sel = xb.pool_select(y, coef[2], coef[3])
+    r = (coef[2].double() * xb.windows(y.double()) + coef[3].double()).clamp_min(0)
+    ties = (r == best.unsqueeze(3)).sum(3) > 1
+    assert float(ties.double().mean()) > 0.2 and float((ties & (best > 0)).double().mean()) > 0.05
+    assert float((best <= 0).double().mean()) > 0.1
+    assert bool((sel[..., 0].sum(3) == 1).all()) and bool(sel[:, :, :, 0, 0].all())  # gamma = 0: position 0 wins
+    s_dz, s_dzx, _, _ = xb.bwd_sums_ref(y, dP, coef, exact_regime=True)
+    dy, _, _, _ = xb.apply_ref(y, dP, coef, gamma, s_dz, s_dzx, B * H * H, exact_regime=True)
+    assert float((dy.float().to(BF16).double() != dy).double().mean()) > 0.1
+
+
+def test_bn_bounds_hold_for_fp32_arithmetic_and_catch_misrouting():
+    """A plain fp32 evaluation of the kernels' formulas stays inside the
+    coefficient, sum and dy bounds on the hard channels (negative gamma, a
+    constant channel, mean 64 with deviation 1/4); one gradient routed to the
+    neighbouring window position, or one dropped item, is outside them."""
+    B, H, C, eps, mom = 8, 16, 32, 1e-3, 0.1
+    g = torch.Generator().manual_seed(13)
+    y = torch.randn(B, H, H, C, generator=g) * 2 + 0.5
+    y[..., 1] = 1.5
+    y[..., 2] = 64 + 0.25 * torch.randn(B, H, H, generator=g)
+    y = y.to(BF16)
+    gamma = (torch.rand(C, generator=g) + 0.5) * torch.where(torch.arange(C) % 3 == 0, -1.0, 1.0)
+    beta, bias = torch.randn(C, generator=g) * 0.1, torch.randn(C, generator=g) * 0.1
+    M = B * H * H
+    yf = y.float().reshape(-1, C)
+    sums = torch.stack([yf.sum(0), (yf * yf).sum(0)])
+    mean = sums[0] / M
+    var = (sums[1] / M - mean * mean).clamp_min(0)
+    invstd = (var + torch.tensor(eps)).rsqrt()
+    sc = gamma * invstd
+    coef = torch.stack([mean, invstd, sc, beta - mean * sc])
+    rm, rv = torch.zeros(C), torch.ones(C)
+    rm2 = (1 - torch.tensor(mom)) * rm + torch.tensor(mom) * (mean + bias)
+    rv2 = (1 - torch.tensor(mom)) * rv + torch.tensor(mom) * (var * M / (M - 1))
+    xb.assert_coefficients(coef, (rm2, rv2), sums, M, gamma, beta, bias, eps, mom, (rm, rv))
+    ref, bnd = xb.bn_coefficient_bounds(sums, M, gamma, beta, bias, eps, mom, (rm, rv))
+    assert float(bnd["invstd"][2] / ref["invstd"][2]) < 0.05  # the mean-64 channel: percent, not ulps
+    assert float((bnd["invstd"] / ref["invstd"])[3:].max()) < 1e-5
+    bad = coef.clone()
+    bad[1, 5] *= 1 + 1e-4
+    with pytest.raises(AssertionError):
+        xb.assert_coefficients(bad, None, sums, M, gamma, beta, bias, eps, mom, (rm, rv))
+    # backward in fp32
+    dP = torch.randn(B, H // 2, H // 2, C, generator=g).to(BF16)
+    dz64, xhat64 = xb.bwd_terms(y, dP, coef)
+    dz, yw = dz64.float(), xb.windows(y.float())
+    s_dz, s_dzx = dz.sum((0, 1, 2, 3)), (dz * (yw - coef[0]) * coef[1]).sum((0, 1, 2, 3))
+    r_dz, r_dzx, a_dz, a_dzx = xb.bwd_sums_ref(y, dP, coef)
+    n_pix = B * (H // 2) ** 2
+    xb.assert_within(s_dz, r_dz, xb.sums_bound(n_pix, a_dz), "sum dz")
+    xb.assert_within(s_dzx, r_dzx, xb.sums_bound(n_pix, a_dzx), "sum dz*xhat")
+    drop = s_dz - dz[-1, -1, -1].sum(0)  # the last item of a grid-stride loop left out
+    with pytest.raises(AssertionError):
+        xb.assert_within(drop, r_dz, xb.sums_bound(n_pix, a_dz), "sum dz")
+    a = gamma * coef[1]
+    kbi, kc = -a * s_dzx * (1.0 / M) * coef[1], -a * s_dz * (1.0 / M)
+    dy = xb.unwindows(a * dz + kbi * (yw - coef[0]) + kc).to(BF16)
+    ref_dy, m_a, m_b, m_c = xb.apply_ref(y, dP, coef, gamma, s_dz, s_dzx, M)
+    xb.assert_within(dy, ref_dy, xb.apply_bound(ref_dy, m_a, m_b, m_c, 1), "dy")
+    sel = dz64 != 0
+    b_, i_, j_, c_ = [int(v[0]) for v in torch.nonzero(sel[:, :, :, 0, :] & (dz64[:, :, :, 0, :].abs() > 0.5), as_tuple=True)]
+    wrong = xb.windows(dy.float()).clone()
+    ka = float(a[c_] * dz[b_, i_, j_, 0, c_])
+    wrong[b_, i_, j_, 0, c_] -= ka  # the gradient of one window lands on the next position
+    wrong[b_, i_, j_, 1, c_] += ka
+    with pytest.raises(AssertionError):
+        xb.assert_within(xb.unwindows(wrong).to(BF16), ref_dy, xb.apply_bound(ref_dy, m_a, m_b, m_c, 1), "dy")
+
+
+def test_head_exact_inputs_and_reference():
+    """The head's exact regime holds at the largest shape (representability
+    asserted inside), the reference equals fp64 autograd, and dh on those
+    inputs is (W[max] - W[label]) / B."""
+    g = torch.Generator().manual_seed(14)
+    h, w, b, lab, k = xb.head_exact_inputs(128, 4096, g)
+    r = xb.head_exact_ref(h, w, b, lab)
+    assert bool((r["logits"].argmax(1) == k).all()) and {0, 9} <= set(lab.tolist()) and {0, 9} <= set(k.tolist())
+    assert 0.3 < float((lab == k).double().mean()) < 0.7
+    assert torch.equal(r["dh"], (w.double()[k] - w.double()[lab]) / 128)
+    assert torch.equal(r["loss_b"], r["logits"].max(1).values - r["logits"][torch.arange(128), lab])
+    h2 = torch.randn(5, 264, generator=g).to(BF16)
+    w2, b2 = torch.randn(10, 264, generator=g) * 0.02, torch.randn(10, generator=g) * 0.1
+    lab2 = torch.randint(0, 10, (5,), generator=g)
+    r2 = xb.head_ref(h2, w2, b2, lab2)
+    hr, wr, br = (t.double().requires_grad_(True) for t in (h2, w2, b2))
+    lp = F.log_softmax(F.linear(hr, wr, br), 1)
+    F.nll_loss(lp, lab2).backward()
+    for got, want in ((r2["logp"], lp), (r2["dh"], hr.grad), (r2["dW"], wr.grad), (r2["db"], br.grad)):
+        torch.testing.assert_close(got, want.detach(), rtol=1e-12, atol=1e-14)
