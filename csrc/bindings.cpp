@@ -151,6 +151,10 @@ PYBIND11_MODULE(_C, m) {
   m.def("bn_bwd_reduce_head", &bn_bwd_reduce_head);
   m.def("bn_bwd_reduce_slab", &bn_bwd_reduce_slab);
   m.def("head_wgrad", &head_wgrad);
+  m.def("eval_head", &eval_head, py::arg("y"), py::arg("coef"), py::arg("yH"), py::arg("yW"), py::arg("yC"),
+        py::arg("w"), py::arg("bias"), py::arg("labels"), py::arg("B"), py::arg("NC"), py::arg("ctr"),
+        py::arg("n_order"), py::arg("n_valid"), py::arg("pred"), py::arg("nll"), py::arg("mat"),
+        py::arg("logits_out"), py::arg("stream"));
   m.def("mnist_step", &mnist_step);
   m.def("mnist_scratch_bytes", &mnist_scratch_bytes);
   m.def("maxpool_bn_bwd", &maxpool_bn_bwd);

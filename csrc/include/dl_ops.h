@@ -251,6 +251,16 @@ void bn_bwd_apply_head(uintptr_t y, uintptr_t dP, uintptr_t coef, uintptr_t dgb,
 void head_wgrad(uintptr_t h, uintptr_t dlogits, uintptr_t loss_b, int F, int B, int NC, uintptr_t dw, uintptr_t db,
                 uintptr_t loss, uintptr_t slot, uintptr_t step_ctr, uintptr_t stream);
 
+// eval_head.hip -----------------------------------------------------------------
+// Evaluation head of the reference net: eval-mode BN/ReLU/pool of the last block
+// + Linear + log-softmax (bitwise predict's), then per-sample metrics.  Row b of
+// step ctr[0] is position (ctr[0]*B + b) mod n_order; rows at positions
+// < n_valid write pred / nll there and count in mat, the others write nothing.
+// The launch advances ctr[0] by one (arrival ticket on ctr[1]).
+void eval_head(uintptr_t y, uintptr_t coef, int yH, int yW, int yC, uintptr_t w, uintptr_t bias, uintptr_t labels,
+               int B, int NC, uintptr_t ctr, int n_order, int n_valid, uintptr_t pred, uintptr_t nll, uintptr_t mat,
+               uintptr_t logits_out, uintptr_t stream);
+
 // pool_nhwc.hip ----------------------------------------------------------------
 // stem max-pool backward fused with its input BN + ReLU's backward (pool_nhwc.hip)
 void maxpool_bn_bwd(uintptr_t dy, uintptr_t idx, uintptr_t x, uintptr_t save, uintptr_t w, uintptr_t b,

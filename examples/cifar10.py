@@ -15,8 +15,13 @@ epoch runs on the same fast path as bench.py: a device-side label-uniform
 sampler (``DeviceLoader``) whose batch is gathered + normalised inside the
 step, ``trainer.run`` replaying unrolled multi-step graphs, and the
 every-sample training confusion matrix updated by a kernel captured in the
-step (``trainer.step_hooks``).  Without the dataset files (``--data`` directory with
-the CIFAR-10 binary release) synthetic CIFAR-shaped data is used.
+step (``trainer.step_hooks``).  ``--testPath device`` evaluates the test
+partition on the device as well (``DeviceEvalLoader`` + ``trainer.evaluate``:
+every test sample exactly once, replayed forward-only hipGraphs, no host work
+per batch); the default ``batcher`` keeps the host-sampled predict loop, whose
+padded last batch counts its repeated rows.  Without the dataset files
+(``--data`` directory with the CIFAR-10 binary release) synthetic CIFAR-shaped
+data is used.
 
     python -m torch_distlearn_amd.launch --nproc 2 examples/cifar10.py --epochs 1
 """
@@ -32,7 +37,7 @@ import torch  # noqa: E402
 
 from torch_distlearn_amd import LocalhostTree  # noqa: E402
 from torch_distlearn_amd.checkpoint import results_dir, resume_trainer, save_trainer  # noqa: E402
-from torch_distlearn_amd.data import Dataset, DeviceLoader  # noqa: E402
+from torch_distlearn_amd.data import Dataset, DeviceEvalLoader, DeviceLoader  # noqa: E402
 from torch_distlearn_amd.engine import DataParallelTrainer  # noqa: E402
 from torch_distlearn_amd.launch import (add_checkpoint_flags, add_node_flags, add_schedule_flags,  # noqa: E402
                                         device_of, node_opts, quiet_unless_root)
@@ -54,6 +59,10 @@ def main():
     ap.add_argument("--graph", type=int, default=1)
     ap.add_argument("--unroll", type=int, default=16, help="steps per replayed hipGraph (HIP fast path)")
     ap.add_argument("--metrics", default=None, help="JSON-lines metrics file (node 1)")
+    ap.add_argument("--testPath", default="batcher", choices=["batcher", "device"],
+                    help="test-set evaluation: the host-sampled predict loop, or the device-resident pass "
+                         "(trainer.evaluate: every test sample exactly once, replayed forward-only hipGraphs "
+                         "on the HIP fast path)")
     add_checkpoint_flags(ap)
     add_schedule_flags(ap)
     opt = ap.parse_args()
@@ -76,6 +85,7 @@ def main():
     else:
         train_b = train.sampledBatcher("label-uniform", per_node, dtype=dt, seed=opt.seed + opt.nodeIndex)
     test_b = test.sampledBatcher("linear", per_node, dtype=dt)
+    test_l = DeviceEvalLoader(test, per_node) if opt.testPath == "device" else None
 
     torch.manual_seed(0)  # same init on all nodes (cifar10.lua:105)
     model = CifarConvNet(seed=0).to(dev)
@@ -97,6 +107,8 @@ def main():
         # argmax+histogram kernel inside every captured step
         trainer.step_hooks.append(conf.add)
         trainer.prepare(train_b, opt.unroll)  # all captures happen here, before any timed epoch
+    if test_l is not None:
+        trainer.prepare_eval(test_l, opt.unroll)  # the evaluation graphs too (a no-op off the HIP graph path)
 
     for epoch in range(first, opt.epochs + 1):
         conf.zero()
@@ -122,13 +134,21 @@ def main():
         print(f"Epoch {epoch}: learning rate {trainer.lr:.8g} (last of {nb} steps; --lrSchedule {opt.lrSchedule})")
         trainer.synchronize()  # cifar10.lua:208
         conf.zero()
-        ntb = test_b.numBatches() if not opt.maxSteps else min(opt.maxSteps, test_b.numBatches())
-        test_b.reset()
-        for _ in range(ntb):
-            x, y = test_b.getBatch()
-            conf.add(trainer.predict(x), y)
+        if test_l is not None:
+            res = trainer.evaluate(test_l, conf, unroll=opt.unroll)  # the whole test partition, each sample once
+            nll_sum = res["loss_sum"].reshape(1).clone()
+            tree.allReduce([nll_sum], "sum")
+        else:
+            ntb = test_b.numBatches() if not opt.maxSteps else min(opt.maxSteps, test_b.numBatches())
+            test_b.reset()
+            for _ in range(ntb):
+                x, y = test_b.getBatch()
+                conf.add(trainer.predict(x), y)
         conf.allReduce(tree)  # cifar10.lua:234
         print(f"Epoch {epoch}: test accuracy {100 * conf.totalValid:.2f}%")
+        if test_l is not None:
+            count = int(conf.mat.sum())  # over all nodes: each test sample exactly once
+            print(f"Epoch {epoch}: evaluated {count} test samples, mean NLL {float(nll_sum) / max(count, 1):.4f}")
         log.log(epoch=epoch, loss=float(loss), images_per_s=nb * per_node * opt.numNodes / dt_s,
                 test_acc=conf.totalValid)
         if opt.save:

@@ -312,6 +312,82 @@ class DeviceLoader:
     get_batch = getBatch
 
 
+class DeviceEvalLoader:
+    """Device-resident single pass over this node's partition, in order, for
+    evaluation (``DataParallelTrainer.evaluate``).
+
+    ``order`` holds the partition's sample indices ``lo .. hi-1`` followed by
+    the last index repeated up to ``steps * batch`` entries (what the linear
+    sampler emits), so step ``s`` reads ``order[s*B .. s*B + B)`` through the
+    same device step counter and the same gather kernel as
+    :class:`DeviceLoader`; only positions below ``n_valid`` count.  The
+    evaluation head writes each sample's prediction and negative
+    log-likelihood at its position (``pred``, ``nll``) and accumulates the
+    confusion matrix ``mat``; :meth:`reset` rewinds all of it with device-side
+    fills (no host synchronisation, no host->device copy).  ``ctr[1]`` is the
+    head kernel's arrival word (zero between launches).
+
+    Works on CPU tensors too (the constructor makes no native call).
+    """
+
+    PRED_RESET = -1  # what reset() leaves in ``pred`` (no class); ``nll`` resets to 0
+
+    def __init__(self, ds: PartitionedDataset, batch: int = 32):
+        self.ds, self.batch = ds, int(batch)
+        if self.batch <= 0:
+            raise ValueError("batch must be positive")
+        self.H, self.W = ds.H, ds.W
+        self.lo = ds.N * (ds.partition - 1) // ds.partitions
+        self.hi = ds.N * ds.partition // ds.partitions
+        self.n_valid = int(ds.size())
+        if self.n_valid != self.hi - self.lo or self.n_valid <= 0:
+            raise ValueError("empty partition")
+        self.steps = (self.n_valid + self.batch - 1) // self.batch
+        self.n_order = self.steps * self.batch
+        order = torch.full((self.n_order,), self.hi - 1, dtype=torch.int32)
+        order[:self.n_valid] = torch.arange(self.lo, self.hi, dtype=torch.int32)
+        dev = ds.device
+        self.order = order.to(dev)
+        self.ctr = torch.zeros(2, dtype=torch.int64, device=dev)  # [step, arrival word of the head kernel]
+        self.labels_out = torch.zeros(self.batch, dtype=torch.int64, device=dev)
+        self.pred = torch.full((self.n_order,), self.PRED_RESET, dtype=torch.int32, device=dev)
+        self.nll = torch.zeros(self.n_order, dtype=torch.float32, device=dev)
+        self.mat = torch.zeros(ds.num_classes, ds.num_classes, dtype=torch.int64, device=dev)
+
+    def numBatches(self) -> int:  # noqa: N802
+        return self.steps
+
+    num_batches = numBatches
+
+    def reset(self) -> None:
+        """Rewind: step counter, confusion matrix and per-sample results
+        (stream-ordered device fills)."""
+        self.ctr.zero_()
+        self.mat.zero_()
+        self.pred.fill_(self.PRED_RESET)
+        self.nll.zero_()
+
+    def gather_args(self):
+        ds = self.ds
+        return (ds.images.data_ptr(), self.order.data_ptr(), ds.labels.data_ptr(), self.labels_out.data_ptr(),
+                self.ctr.data_ptr(), int(self.n_order), ds.C, [float(v) for v in ds.mean[:ds.C]],
+                [float(v) for v in ds.std[:ds.C]])
+
+    def host_batch(self, k: int) -> Tuple[torch.Tensor, torch.Tensor, int]:
+        """Batch ``k`` gathered eagerly (paths without the native executor):
+        (x NHWC normalised fp32, y int64, valid) -- only the first ``valid``
+        rows are samples of the partition, the rest repeat the last one."""
+        if not 0 <= k < self.steps:
+            raise IndexError(f"batch {k} of {self.steps}")
+        idx = self.order[k * self.batch:(k + 1) * self.batch].to(torch.int64)
+        ds = self.ds
+        x = ds.images.index_select(0, idx).float().div_(255.0)
+        mean = torch.tensor(ds.mean[:ds.C], dtype=torch.float32, device=x.device)
+        std = torch.tensor(ds.std[:ds.C], dtype=torch.float32, device=x.device)
+        x = (x - mean) / std
+        return x, ds.labels.index_select(0, idx), min(self.batch, self.n_valid - k * self.batch)
+
+
 # ---------------------------------------------------------------------------
 # sources
 # ---------------------------------------------------------------------------

@@ -232,6 +232,9 @@ class DataParallelTrainer:
         self._multi = {}     # unroll -> (graph, loss) (run())
         self._seqs = {}      # id(graph) -> collectives recorded at its capture (DISTLEARN_DEBUG_SYNC)
         self.captures = 0    # hipGraph captures so far (none may happen in a timed region)
+        self._eval_graphs = {}     # steps -> forward-only graph on _eval_loader (evaluate())
+        self._eval_loader = None
+        self.eval_captures = 0     # captures of those (``captures`` counts training graphs only)
         self.last_loss: Optional[torch.Tensor] = None
         self.steps = 0
         # callables hook(logits, labels) run INSIDE every step body, after the
@@ -633,6 +636,7 @@ class DataParallelTrainer:
             # graphs holding the old communicator's collectives go first
             self._graph, self._static = None, None
             self._multi = {}
+            self._drop_eval_graphs()
             comm.set_channel_cap(cap)
         self._set_policy(kw)
 
@@ -663,6 +667,7 @@ class DataParallelTrainer:
         self.executor.set_policy(**kw)
         self._graph, self._static = None, None
         self._multi = {}
+        self._drop_eval_graphs()  # they would replay on the freed workspaces too
         if self._slabs is not None:  # the re-planned workspaces have new slabs
             self._slabs = self.executor.defer_slab_reduce() or None
             self._arm_side_update()
@@ -881,6 +886,103 @@ class DataParallelTrainer:
             self.sgd.stepsPerNode[self.tree.nodeIndex - 1] -= 3
         self._restore(saved, x)
         self._graph, self._static = g, (sx, sy, loss)
+
+    # ------------------------------------------------------------------ evaluation
+    def _drop_eval_graphs(self) -> None:
+        self._eval_graphs, self._eval_loader = {}, None
+
+    def _eval_native(self) -> bool:
+        """Whether evaluation runs on the executor's device path (eval_step)."""
+        return callable(getattr(self.executor, "eval_step", None))
+
+    def _eval_sizes(self, unroll: int):
+        return sorted(set(self._unroll_sizes(max(1, int(unroll)))) | {1})
+
+    def prepare_eval(self, loader, unroll: int = 16) -> None:
+        """Capture the forward-only hipGraphs :meth:`evaluate` replays on
+        ``loader`` (a :class:`~torch_distlearn_amd.data.DeviceEvalLoader`):
+        ``_unroll_sizes(unroll)`` and 1 evaluation steps each, single-stream,
+        no collective.  Idempotent; a no-op off the native graph path.
+        Changes no training state; leaves ``loader`` rewound."""
+        if not (self.graph and self._eval_native()):
+            return
+        if self._eval_loader is not loader:
+            self._drop_eval_graphs()
+            self._eval_loader = loader
+        new = [k for k in self._eval_sizes(unroll) if k not in self._eval_graphs]
+        if not new:
+            return
+        ex = self.executor
+        # a training graph never ends on a step that prepared the next one (prep_next
+        # applies inside a graph only), so the input buffers are free between two runs
+        assert not getattr(ex, "_prepared", False), "evaluation inside a prepared-ahead training step"
+        # one eager step first: nothing is loaded or allocated for the first time inside a capture
+        loader.reset()
+        ex.eval_begin()
+        ex.eval_step(loader)
+        for k in new:
+            g = torch.cuda.CUDAGraph()
+            with _capturing(self.tree.comm), torch.cuda.graph(g, capture_error_mode=_CAPTURE_MODE):
+                for _ in range(k):
+                    ex.eval_step(loader)
+            self.eval_captures += 1
+            self._eval_graphs[k] = g
+        loader.reset()
+
+    @torch.no_grad()
+    def evaluate(self, loader, conf=None, unroll: int = 16) -> dict:
+        """One pass over ``loader``'s partition, every sample exactly once (the
+        padded rows of the last batch do not count): the reference's per-epoch
+        test loop (examples/cifar10.lua:213-231).  Returns ``{"mat": int64
+        [C, C] confusion counts, "count": samples evaluated (host int),
+        "loss_sum": summed negative log-likelihood, "pred": [count] predicted
+        classes, "nll": [count] per-sample losses}`` as device tensors; nothing
+        waits for the device.  ``conf`` (a ConfusionMatrix): ``conf.mat +=
+        mat`` (the caller all-reduces it).  Changes no training state.
+
+        Native executor: the loader's device step counter selects each batch,
+        the evaluation head writes the results in place; ``graph=True``
+        replays forward-only graphs of up to ``unroll`` steps (captured on
+        first use, or ahead of time by :meth:`prepare_eval`), else the same
+        steps run eagerly.  Any other backend: a loop over the partition in
+        order with :meth:`predict`."""
+        if not hasattr(loader, "n_valid"):
+            raise TypeError("evaluate needs a DeviceEvalLoader")
+        n = loader.n_valid
+        if self._eval_native():
+            ex = self.executor
+            if self.graph:
+                self.prepare_eval(loader, unroll)
+            assert not getattr(ex, "_prepared", False), "evaluation inside a prepared-ahead training step"
+            loader.reset()
+            ex.eval_begin()
+            left = loader.steps
+            while left > 0:
+                k = max((u for u in self._eval_graphs if u <= left), default=0) if self.graph else 0
+                if k:
+                    self._eval_graphs[k].replay()
+                else:
+                    ex.eval_step(loader)
+                    k = 1
+                left -= k
+            mat, pred, nll = loader.mat.clone(), loader.pred[:n].clone(), loader.nll[:n].clone()
+        else:
+            preds, nlls = [], []
+            for k in range(loader.steps):
+                x, y, valid = loader.host_batch(k)
+                logp = self.predict(x.to(self.compute_dtype)).float()[:valid]
+                preds.append(logp.argmax(dim=1).to(torch.int32))
+                nlls.append(-logp.gather(1, y[:valid].unsqueeze(1)).squeeze(1))
+            pred, nll = torch.cat(preds), torch.cat(nlls)
+            nc = loader.mat.shape[0]
+            mat = torch.zeros_like(loader.mat)
+            idx = loader.ds.labels[loader.lo:loader.hi] * nc + pred.to(torch.int64)
+            mat.view(-1).index_add_(0, idx, torch.ones_like(idx))
+        if conf is not None:
+            if conf.mat.device != mat.device:
+                conf.mat = conf.mat.to(mat.device)
+            conf.mat += mat
+        return {"mat": mat, "count": n, "loss_sum": nll.sum(), "pred": pred, "nll": nll}
 
     # ------------------------------------------------------------------ epoch end
     def synchronize(self) -> None:

@@ -280,6 +280,8 @@ class CifarHIPExecutor:
         # while the main stream writes dy_{i-1}
         self.dYs = [torch.zeros(B, h + P2, h + P2, c, dtype=BF16, device=d) for h, c in zip(self.hs, self.couts)]
         self.coef = [torch.empty(4, c, device=d) for c in self.couts]
+        # evaluation's own coefficient rows (eval_begin / eval_step): training's coef is never written by it
+        self.eval_coef = [torch.empty(4, c, device=d) for c in self.couts]
         self.acoef = [torch.empty(3, c, device=d) for c in self.couts]
         self.fwd_plan, self.stats = [], []
         # mode 2: R zeroed [2][C] (sum, sumsq) rows per layer in one arena, and R
@@ -392,9 +394,11 @@ class CifarHIPExecutor:
                          self.cins_real[0], self.w1_cp, *tw, *self._zero_args(train), s)
         return B
 
-    def _forward(self, B: int, s: int, train: bool, pool_last: bool = True):
+    def _forward(self, B: int, s: int, train: bool, pool_last: bool = True, coef=None):
         """Conv -> BN finalize -> BN/ReLU/pool per block.  ``pool_last=False``
         leaves the last block's pool to the head kernel (head_fwd_bwd_pool).
+        ``coef`` (eval mode only): coefficient rows derived beforehand
+        (eval_begin) -- no finalize launch runs and ``self.coef`` is not touched.
         (Block i-1's BN/ReLU/pool applied on load by block i's conv measured a
         wash -- 25.9 us for the fused conv vs 18.1 + 8.2 us, both bound by the
         one read of the pre-BN output, profiles/r4_pool_on_load_ab.txt --
@@ -417,7 +421,10 @@ class CifarHIPExecutor:
                                  self.stats[i].data_ptr() if train else 0, self.slabs.data_ptr(), B, h, h,
                                  self.kin0 if i == 0 else cin, cout, KSIZE, t, sp, s)
             fused = train and self.atomic  # coefficients derived by the consumer kernel
-            if not fused:
+            if coef is not None:
+                cf = coef[i]
+            elif not fused:
+                cf = self.coef[i]
                 C.bn_finalize(self.stats[i].data_ptr(), ntm, cout, M, self.p32[self._leaf(i, 2)].data_ptr(),
                               self.p32[self._leaf(i, 3)].data_ptr(), self.p32[self._leaf(i, 1)].data_ptr(),
                               self.rm[i].data_ptr(), self.rv[i].data_ptr(), BN_EPS, BN_MOMENTUM, 0 if train else 1,
@@ -428,7 +435,7 @@ class CifarHIPExecutor:
                     C.bn_relu_pool_fwd_fin(self.y[i].data_ptr(), *self._fin_args(i, M), self.p[i].data_ptr(), B, h,
                                            h, cout, opad, s)
                 else:
-                    C.bn_relu_pool_fwd(self.y[i].data_ptr(), self.coef[i].data_ptr(), self.p[i].data_ptr(), B, h, h,
+                    C.bn_relu_pool_fwd(self.y[i].data_ptr(), cf.data_ptr(), self.p[i].data_ptr(), B, h, h,
                                        cout, opad, s)
             inp = self.p[i]
 
@@ -831,6 +838,52 @@ class CifarHIPExecutor:
     def _ready(self, leaf: int):
         if self.bucketer is not None:
             self.bucketer.mark_leaf_ready(leaf)
+
+    # ------------------------------------------------------------------ evaluation
+    def eval_begin(self) -> None:
+        """Once per evaluation: the eval-mode BN coefficients of every block
+        (running statistics, bn_finalize mode 1) into ``eval_coef`` -- what
+        predict derives again for every batch."""
+        s = stream_handle()
+        for i in range(self.nb):
+            self.C.bn_finalize(0, 0, self.couts[i], 1, self.p32[self._leaf(i, 2)].data_ptr(),
+                               self.p32[self._leaf(i, 3)].data_ptr(), self.p32[self._leaf(i, 1)].data_ptr(),
+                               self.rm[i].data_ptr(), self.rv[i].data_ptr(), BN_EPS, BN_MOMENTUM, 1,
+                               self.eval_coef[i].data_ptr(), s)
+
+    def eval_step(self, loader, logits_out: Optional[torch.Tensor] = None) -> None:
+        """One forward-only step on a :class:`~torch_distlearn_amd.data.DeviceEvalLoader`
+        (after :meth:`eval_begin`): gather the batch the loader's device step
+        counter selects, the eval-mode forward on predict's convolution plans
+        with the coefficients of ``eval_coef`` (no finalize launch), and the
+        evaluation head (csrc eval_head.hip), which writes the batch's
+        predictions / losses / confusion counts into the loader and advances
+        its counter.  Capturable; writes no training state (``logits``,
+        ``coef``, running statistics, the training loader).  ``logits_out``
+        (tests): fp32 [batch, classes] for the valid rows' log-probabilities."""
+        if not hasattr(loader, "n_valid") or not hasattr(loader, "gather_args"):
+            raise TypeError("eval_step needs a DeviceEvalLoader")
+        if not self.head_pool:
+            raise RuntimeError("eval_step: the evaluation head is built for the reference net "
+                               "(2048 pooled features, 10 classes)")
+        # prep_next hands a batch over only inside a training graph: a pending one would be overwritten here
+        assert not self._prepared, "eval_step between a training step and the step its update prepared"
+        if tuple(loader.mat.shape) != (self.nclass, self.nclass):
+            raise ValueError("the loader's confusion matrix does not match the model's classes")
+        lo = 0
+        if logits_out is not None:
+            if (logits_out.dtype != torch.float32 or not logits_out.is_contiguous()
+                    or logits_out.numel() < loader.batch * self.nclass):
+                raise ValueError("logits_out must be contiguous fp32 [batch, classes]")
+            lo = logits_out.data_ptr()
+        s = stream_handle()
+        B = self._prep(loader, s, train=False)
+        self._forward(B, s, train=False, pool_last=False, coef=self.eval_coef)
+        hl, nfc = self.hs[-1], 4 * self.nb
+        self.C.eval_head(self.y[-1].data_ptr(), self.eval_coef[-1].data_ptr(), hl, hl, self.couts[-1],
+                         self.p32[nfc].data_ptr(), self.p32[nfc + 1].data_ptr(), loader.labels_out.data_ptr(), B,
+                         self.nclass, loader.ctr.data_ptr(), loader.n_order, loader.n_valid, loader.pred.data_ptr(),
+                         loader.nll.data_ptr(), loader.mat.data_ptr(), lo, s)
 
     @torch.no_grad()
     def predict(self, x: torch.Tensor, batch_stats: bool = False) -> torch.Tensor:
