@@ -308,6 +308,9 @@ void sgd_update_slabs(uintptr_t p, uintptr_t g, uintptr_t mom, uintptr_t p16, ui
                             lr_dev);
   if (skip_hi > skip_lo) {
     if (skip_lo % 4 || skip_hi % 4 || skip_lo < 0 || skip_hi > n) throw std::runtime_error("sgd_update_slabs: bad skip");
+    // the tail blocks do not consult the skip: a skipped tail element would be updated twice in a step
+    if (job.r.tail_nblk > 0 && skip_lo / 4 < job.r.tail_hi4 && job.r.tail_lo4 < skip_hi / 4)
+      throw std::runtime_error("sgd_update_slabs: the skip overlaps the tail");
     job.skip_lo4 = skip_lo / 4;
     job.skip_hi4 = skip_hi / 4;
     // a skipped suffix (the side job's range): the grid covers only the rest

@@ -342,3 +342,237 @@ def test_head_exact_inputs_and_reference():
     F.nll_loss(lp, lab2).backward()
     for got, want in ((r2["logp"], lp), (r2["dh"], hr.grad), (r2["dW"], wr.grad), (r2["db"], br.grad)):
         torch.testing.assert_close(got, want.detach(), rtol=1e-12, atol=1e-14)
+
+
+# ---------------------------------------------------------------------------
+# the update / slab-sum / pack / gather references (tests/kernels/exact_update.py)
+# ---------------------------------------------------------------------------
+import fractions  # noqa: E402
+
+import numpy as np  # noqa: E402
+
+from tests.kernels import exact_update as xu  # noqa: E402
+
+
+def _round_fraction_to_f32(q):
+    """fp32 nearest (ties to even) to the exact rational q, by integer arithmetic."""
+    if q == 0:
+        return np.float32(0.0)
+    sign, q = (-1 if q < 0 else 1), abs(q)
+    e = q.numerator.bit_length() - q.denominator.bit_length()
+    if fractions.Fraction(2) ** e > q:
+        e -= 1
+    assert fractions.Fraction(2) ** e <= q < fractions.Fraction(2) ** (e + 1)
+    e = max(e, -126)  # subnormals share the smallest normal's spacing
+    scaled = q / fractions.Fraction(2) ** (e - 23)  # integer part: the 24-bit significand
+    n, rest = divmod(scaled.numerator, scaled.denominator)
+    twice = 2 * rest
+    if twice > scaled.denominator or (twice == scaled.denominator and n & 1):
+        n += 1
+    return np.float32(sign * float(n) * 2.0 ** (e - 23))
+
+
+def test_fma32_matches_exact_rational_arithmetic():
+    rng = np.random.default_rng(7)
+    n = 3000
+    a = (rng.standard_normal(n) * 2.0 ** rng.integers(-12, 12, n)).astype(np.float32)
+    b = (rng.standard_normal(n) * 2.0 ** rng.integers(-12, 12, n)).astype(np.float32)
+    c = (rng.standard_normal(n) * 2.0 ** rng.integers(-30, 30, n)).astype(np.float32)
+    c[::3] = (-a[::3].astype(np.float64) * b[::3]).astype(np.float32)  # cancellation: the low product bits decide
+    got = xu.fma32(a, b, c)
+    F = fractions.Fraction
+    for i in range(n):
+        want = _round_fraction_to_f32(F(float(a[i])) * F(float(b[i])) + F(float(c[i])))
+        assert got[i].view(np.uint32) == want.view(np.uint32), (i, a[i], b[i], c[i], got[i], want)
+
+
+def test_fma32_double_rounding_case():
+    """a = b = 1 + 2^-12, c = 2^-60: a b = 1 + 2^-11 + 2^-24, an fp32 tie between
+    1 + 2^-11 (even) and 1 + 2^-11 + 2^-23; c lifts it just above, so the one
+    rounding goes up.  fp64(a b + c) loses c, and its fp32 rounding ties to
+    even: down.  Mirrored below the tie with -c."""
+    a = np.float32(1 + 2.0 ** -12)
+    c = np.float32(2.0 ** -60)
+    up, down = np.float32(1 + 2.0 ** -11 + 2.0 ** -23), np.float32(1 + 2.0 ** -11)
+    assert xu.fma32(a, a, c) == up
+    assert np.float32(np.float64(a) * np.float64(a) + np.float64(c)) == down  # the rejected reference
+    assert xu.fma32(a, a, -c) == down
+    # an odd neighbour: a b = 1 + 3 2^-12 + ... chosen so that the tie's even side is up
+    a2, b2 = np.float32(1 + 2.0 ** -12), np.float32(1 + 2.0 ** -11 + 2.0 ** -12)
+    exact = fractions.Fraction(float(a2)) * fractions.Fraction(float(b2))
+    for cc in (c, -c):
+        want = _round_fraction_to_f32(exact + fractions.Fraction(float(cc)))
+        assert xu.fma32(a2, b2, cc) == want
+
+
+@pytest.mark.parametrize("mu", [None, 0.5, 0.75])
+@pytest.mark.parametrize("count", [1, 2, 4])
+def test_sgd_ref_exact_regime_is_the_fp64_formula(mu, count):
+    rng = np.random.default_rng(11)
+    n = 4096
+    p, m = (rng.integers(-64, 65, n).astype(np.float32) for _ in range(2))
+    g = rng.integers(-64 * 129, 64 * 129 + 1, n).astype(np.float32)  # up to a 129-split sum of such integers
+    m = None if mu is None else m
+    s = xu.participation_scale(count)
+    assert float(s) == 1.0 / count
+    got_p, got_m = xu.sgd_ref(p, g, m, s, 2.0 ** -3, 2.0 ** -2, mu or 0.0)
+    want_p, want_m = xu.sgd_formula64(p, g, m, count, 2.0 ** -3, 2.0 ** -2, mu or 0.0)
+    assert np.array_equal(got_p.astype(np.float64), want_p)
+    assert (got_m is None) == (want_m is None)
+    if got_m is not None:
+        assert np.array_equal(got_m.astype(np.float64), want_m)
+
+
+def test_participation_scale():
+    assert xu.participation_scale(1.0) == 1.0 and xu.participation_scale(0.0) == 1.0
+    third = xu.participation_scale(3.0)
+    assert third.dtype == np.float32 and third == np.float32(1.0 / 3.0)
+    assert third.view(np.uint32) == 0x3EAAAAAB
+
+
+@pytest.mark.parametrize("splits", sorted(set(xu.INPLACE_SPLITS + xu.TAIL_SPLITS)))
+def test_slab_sum_ref_integer_slabs(splits):
+    rng = np.random.default_rng(splits)
+    slabs = rng.integers(-64, 65, (splits, 40)).astype(np.float32)
+    for tpo in {xu.slab_tpo(splits), 8 if 8 <= splits < 32 else xu.slab_tpo(splits)}:
+        got = xu.slab_sum_ref(slabs, tpo)
+        assert np.array_equal(got.astype(np.int64), slabs.astype(np.int64).sum(0))
+
+
+def test_slab_tpo_thresholds():
+    assert [xu.slab_tpo(k) for k in (1, 7, 8, 31, 32, 129)] == [1, 1, 8, 8, 32, 32]
+
+
+def test_slab_sum_ref_order_is_told_apart():
+    """On real data the lane order matters: blocked instead of strided lanes,
+    an ascending butterfly and a plain sequential sum all differ somewhere."""
+    rng = np.random.default_rng(3)
+    slabs = rng.standard_normal((25, 4096)).astype(np.float32)
+    want = xu.slab_sum_ref(slabs, 8)
+
+    def lanes(parts, orders):
+        for o in orders:
+            parts = [xu.add32(parts[t], parts[t ^ o]) for t in range(8)]
+        return parts[0]
+
+    def part(idx):
+        acc = np.zeros(slabs.shape[1], np.float32)
+        for sp in idx:
+            acc = xu.add32(acc, slabs[sp])
+        return acc
+
+    strided = [part(range(t, 25, 8)) for t in range(8)]
+    assert np.array_equal(lanes(strided, (4, 2, 1)), want)
+    # the spelled-out association
+    p = strided
+    spelled = xu.add32(xu.add32(xu.add32(p[0], p[4]), xu.add32(p[2], p[6])),
+                       xu.add32(xu.add32(p[1], p[5]), xu.add32(p[3], p[7])))
+    assert np.array_equal(spelled, want)
+    blocked = [part(range(4 * t, min(4 * t + 4, 25))) for t in range(8)]  # 7 lanes of 4 (the last: 1), sequential
+    assert not np.array_equal(lanes(blocked, (4, 2, 1)), want)
+    assert not np.array_equal(lanes(strided, (1, 2, 4)), want)
+    assert not np.array_equal(xu.slab_sum_ref(slabs, 1), want)
+    # ... and all agree to rounding
+    assert np.allclose(xu.slab_sum_ref(slabs, 1), want, rtol=0, atol=1e-4)
+
+
+@pytest.mark.parametrize("geom", xu.TAIL_GEOMS + [(4, 25, 8, 3), (4, 25, 16, 3)], ids=str)
+def test_pack1_index_ref_partitions_the_packed_buffer(geom):
+    cout, taps, cp, c = geom
+    e = np.arange(cout * taps * c)
+    idx = xu.pack1_index_ref(e, c, cp)
+    size = xu.pack1_size(cout, taps, cp)
+    assert idx.min() >= 0 and idx.max() < size
+    assert len(np.unique(idx)) == len(e)  # injective
+    pads = np.setdiff1d(np.arange(size), idx)
+    assert len(pads) + len(e) == size
+    if cp > 0:
+        assert np.array_equal(idx, (e // c) * cp + e % c)
+        assert np.all(pads % cp >= c)
+    else:
+        kw = -cp
+        pos = pads % 8  # within a 16-byte pair chunk: [2][4]
+        chunk = (pads // 8) % ((kw + 1) // 2)
+        # a pad is a channel past C, or the second half of an odd row's last chunk
+        assert np.all((pos % 4 >= c) | ((kw % 2 == 1) & (chunk == kw // 2) & (pos >= 4)))
+        # horizontally adjacent taps (kx even, kx + 1) of one row share a chunk
+        w = e.reshape(cout, kw, kw, c)
+        i4 = idx.reshape(cout, kw, kw, c)
+        assert w.shape == i4.shape
+        for kx in range(0, kw - 1, 2):
+            assert np.array_equal(i4[:, :, kx + 1, :], i4[:, :, kx, :] + 4)
+            assert np.array_equal(i4[:, :, kx, 0] % 8, np.zeros_like(i4[:, :, kx, 0]))
+
+
+def test_bf16_integer_rounding_is_torchs():
+    rng = np.random.default_rng(5)
+    x = (rng.standard_normal(20000) * 2.0 ** rng.integers(-20, 20, 20000)).astype(np.float32)
+    ties = (np.arange(0x3F80, 0x3F80 + 512, dtype=np.uint32) << 16 | 0x8000).view(np.float32)  # exactly half way
+    near = np.concatenate([(ties.view(np.uint32) + 1).view(np.float32), (ties.view(np.uint32) - 1).view(np.float32)])
+    special = np.array([0.0, -0.0, np.inf, -np.inf, 3.3895314e38, 1e-40], dtype=np.float32)
+    for v in (x, ties, -ties, near, special):
+        want = torch.from_numpy(v.copy()).to(BF16).view(torch.int16).numpy().view(np.uint16)
+        assert np.array_equal(xu.bf16_bits(v), want)
+    # NaN stays NaN in both (the payload is the implementation's: torch's differs between its own code paths)
+    nans = np.array([0x7FC00000, 0xFFC00001, 0x7F800001, 0x7FFFFFFF], dtype=np.uint32).view(np.float32)
+    for got in (xu.bf16_bits(nans), torch.from_numpy(nans.copy()).to(BF16).view(torch.int16).numpy().view(np.uint16)):
+        assert np.all((got & 0x7FFF) > 0x7F80)
+    assert np.array_equal(xu.bf16_widen(xu.bf16_bits(ties)).view(np.uint32) & 0x10000, np.zeros(512, np.uint32))  # even
+    # one rounding from fp64 agrees wherever fp32 holds the value
+    assert np.array_equal(xu.bf16_round64(x.astype(np.float64)), xu.bf16_widen(xu.bf16_bits(x)).astype(np.float64))
+
+
+def test_gather_reference_and_exemption_cap():
+    from torch_distlearn_amd.data import CIFAR_MEAN, CIFAR_STD
+
+    u = np.arange(256, dtype=np.uint8)
+    img = np.broadcast_to(u[None, :, None, None], (1, 256, 1, 3)).copy()  # every (value, channel) pair
+    x64, lab = xu.gather_ref(img, [0], np.array([9]), 0, 1, CIFAR_MEAN, CIFAR_STD)
+    assert x64.shape == (1, 256, 1, 3) and lab.tolist() == [9]
+    want = (u[:, None] / 255.0 - np.float32(CIFAR_MEAN).astype(np.float64)) / np.float32(CIFAR_STD).astype(np.float64)
+    assert np.array_equal(x64.reshape(256, 3), want)
+    lo, hi, exempt = xu.gather_allowed(x64, CIFAR_MEAN, CIFAR_STD)
+    assert int(exempt.sum()) <= 8, int(exempt.sum())
+    assert np.all(hi[~exempt] == xu.bf16_round64(x64)[~exempt])
+    # the exempt pairs' two candidates are adjacent bf16 values around a boundary
+    assert np.all(lo[exempt] < hi[exempt])
+    # a plain fp32 evaluation (uncontracted and fma-contracted) lands on an allowed value everywhere
+    r, q = np.float32(1.0 / 255.0), (np.float64(1.0) / np.float32(CIFAR_STD).astype(np.float64)).astype(np.float32)
+    uf = img.astype(np.float32)
+    mean = np.broadcast_to(np.float32(CIFAR_MEAN), uf.shape)
+    for d in (xu.add32(xu.mul32(uf, r), -mean), xu.fma32(uf, r, -mean)):
+        y = xu.bf16_widen(xu.bf16_bits(xu.mul32(d, np.broadcast_to(q, uf.shape)))).astype(np.float64)
+        assert np.all((y == lo) | (y == hi))
+    # the sample index in Python integers: a 32-bit product picks other samples
+    order = list(range(7))
+    step = 2 ** 33 + 5
+    assert xu.gather_samples(order, step, 3) == [(step * 3 + b) % 7 for b in range(3)]
+    assert xu.gather_samples(order, step, 3) != [(((step * 3) & 0xFFFFFFFF) + b) % 7 for b in range(3)]
+    assert xu.gather_samples(order, 2, 3) == [6, 0, 1]  # wraps the ring in the middle of the batch
+
+
+def test_slab_sum_lane_rotation_is_the_same_sum():
+    """Which lane a split lands in matters only up to the butterfly's symmetry:
+    rotating the assignment (split u into lane (u + k) mod 8) or xor-ing it
+    with a constant keeps every pair {t, t ^ 4}, every quad and so -- fp32
+    addition being commutative -- every bit.  A test cannot tell such an edit
+    from the original, and need not.  Halving the lanes (u mod 4) or
+    exchanging two lanes that are not partners is a different sum."""
+    rng = np.random.default_rng(9)
+    slabs = rng.standard_normal((25, 4096)).astype(np.float32)
+    want = xu.slab_sum_ref(slabs, 8)
+
+    def tree(lane_of):
+        parts = [np.zeros(slabs.shape[1], np.float32) for _ in range(8)]
+        for sp in range(slabs.shape[0]):
+            t = lane_of(sp % 8)
+            parts[t] = xu.add32(parts[t], slabs[sp])
+        for o in (4, 2, 1):
+            parts = [xu.add32(parts[t], parts[t ^ o]) for t in range(8)]
+        return parts[0]
+
+    for k in range(1, 8):
+        assert np.array_equal(tree(lambda u: (u + k) % 8), want)
+        assert np.array_equal(tree(lambda u: u ^ k), want)
+    assert not np.array_equal(tree(lambda u: u % 4), want)
+    assert not np.array_equal(tree(lambda u: {1: 2, 2: 1}.get(u, u)), want)

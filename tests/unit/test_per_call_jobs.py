@@ -69,3 +69,12 @@ def test_sgd_update_on_cpu_cannot_carry_next_prep(C):
     with pytest.raises(ValueError, match="fp32 gradient on the GPU"):
         sgd_update_(p, g, 0.1, next_prep=_next_prep(C))
     assert torch.equal(p, torch.ones(8))
+
+
+@pytest.mark.parametrize("skip", [(0, 12), (304, 312), (0, 1200)])
+def test_skip_over_the_slab_tail_is_rejected(C, skip):
+    """The tail blocks do not consult the skip range, so the host refuses a
+    skip that overlaps the tail before it launches anything."""
+    with pytest.raises(RuntimeError, match="skip overlaps the tail"):
+        C.sgd_update_slabs(P, P, 0, 0, 0, 0.1, 0.0, 0.0, 1200, [], [], [], [], [8, 300, 5, 4, 25, 8, 3], P,
+                           skip[0], skip[1], 0)
