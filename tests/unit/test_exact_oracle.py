@@ -12,7 +12,13 @@ The second half checks the BatchNorm + ReLU + pool and head oracles of
 tests/kernels/exact_bn_head.py against fp64 autograd, shows that the integer
 inputs tell the pool rule's wrong variants apart, and that a plain fp32
 evaluation of the kernels' formulas stays inside the derived bounds while a
-misrouted gradient or a dropped item does not."""
+misrouted gradient or a dropped item does not.
+
+The last part does the same for tests/kernels/exact_nhwc.py (the ResNet-50
+path's channels-last BatchNorm, max pool and glue kernels): the BN formulas
+against fp64 autograd, the pool reference against F.max_pool2d's indices, and
+the wrong rules (last-maximum ties, a >= 0 ReLU decision, an unrounded residual
+BN, a dropped row, a swapped stem tap) told apart from the right ones."""
 import functools
 
 import pytest
@@ -576,3 +582,162 @@ def test_slab_sum_lane_rotation_is_the_same_sum():
         assert np.array_equal(tree(lambda u: u ^ k), want)
     assert not np.array_equal(tree(lambda u: u % 4), want)
     assert not np.array_equal(tree(lambda u: {1: 2, 2: 1}.get(u, u)), want)
+
+
+# --------------------------------------------------------------------------- tests/kernels/exact_nhwc.py
+from tests.kernels import exact_nhwc as xn  # noqa: E402
+
+
+@pytest.mark.parametrize("relu,with_res", [(False, False), (True, False), (True, True)])
+def test_nhwc_bn_formulas_match_autograd(relu, with_res):
+    """bn_train64 (built from bn_bwd_sums / bn_dx64, the references of the
+    channels-last BN tests) against fp64 autograd of F.batch_norm, to 1e-12."""
+    g = torch.Generator().manual_seed(3)
+    M, Cc, eps = 77, 16, 1e-3
+    x = torch.randn(M, Cc, generator=g, dtype=torch.float64, requires_grad=True)
+    w = torch.randn(Cc, generator=g, dtype=torch.float64, requires_grad=True)
+    b = torch.randn(Cc, generator=g, dtype=torch.float64, requires_grad=True)
+    res = torch.randn(M, Cc, generator=g, dtype=torch.float64, requires_grad=True) if with_res else None
+    dy = torch.randn(M, Cc, generator=g, dtype=torch.float64)
+    z = F.batch_norm(x, None, None, w, b, True, 0.1, eps)
+    z = z + res if with_res else z
+    y = z.relu() if relu else z
+    y.backward(dy)
+    r = xn.bn_train64(x, w, b, eps, dy, relu, res)
+    for k, want in (("y", y), ("dx", x.grad), ("dw", w.grad), ("db", b.grad)):
+        assert float((r[k] - want.detach()).abs().max()) < 1e-12, k
+    if with_res:
+        assert float((r["dres"] - res.grad).abs().max()) < 1e-12
+
+
+@pytest.mark.parametrize("K,S,P", [(3, 2, 1), (2, 2, 0), (3, 1, 1), (3, 3, 1), (5, 2, 2), (1, 1, 0)])
+@pytest.mark.parametrize("H,W", [(7, 5), (8, 10), (2, 3)])
+def test_nhwc_pool_reference_matches_torch(K, S, P, H, W):
+    """pool_fwd_ref's values and argmax bytes against F.max_pool2d's indices
+    (tied windows included), and pool_bwd_ref against autograd for integer dy."""
+    g = torch.Generator().manual_seed(H * 100 + K)
+    x = (torch.randint(-4, 5, (2, H, W, 8), generator=g).float() / 2)
+    y, arg = xn.pool_fwd_ref(x, K, S, P)
+    xt = x.permute(0, 3, 1, 2).double().requires_grad_(True)
+    yt, it = F.max_pool2d(xt, K, S, P, return_indices=True)
+    assert np.array_equal(y, yt.detach().permute(0, 2, 3, 1).float().numpy())
+    assert np.array_equal(xn.pool_arg_to_flat(arg, H, W, K, S, P), it.permute(0, 2, 3, 1).numpy())
+    dy = torch.randint(-8, 9, tuple(y.shape), generator=g).float()
+    yt.backward(dy.permute(0, 3, 1, 2).double())
+    assert np.array_equal(xn.pool_bwd_ref(dy, arg, H, W, K, S, P), xt.grad.permute(0, 2, 3, 1).float().numpy())
+    if K > 1:  # the last-maximum rule picks other bytes on these tied windows
+        assert not np.array_equal(xn.pool_fwd_ref(x, K, S, P, tie="last")[1], arg)
+
+
+def test_nhwc_pool_backward_order_matters():
+    """Real dy: pool_bwd_ref adds in fp32, oh ascending then ow ascending; the
+    reverse order differs in at least one element of a 3x3 / 1 pool, so the
+    bitwise comparison pins the order."""
+    g = torch.Generator().manual_seed(1)
+    x = torch.zeros(1, 6, 6, 8)  # all tied: every window picks tap 0, so pixel (h, w) collects window (h + 1, w + 1) only
+    x[0, 2, 2] = 5.0             # ... except around the peak, which 9 windows choose
+    _, arg = xn.pool_fwd_ref(x, 3, 1, 1)
+    # (a few bf16 values of one magnitude add exactly in fp32: the order shows only across a wide range)
+    dy = (torch.randn(1, 6, 6, 8, generator=g) * torch.pow(2.0, torch.randint(-14, 15, (1, 6, 6, 8), generator=g))).bfloat16()
+    ref = xn.pool_bwd_ref(dy, arg, 6, 6, 3, 1, 1)
+    d = xn.np32(dy)[0, 1:4, 1:4].reshape(9, 8)
+    fwd = np.zeros(8, np.float32)
+    rev = np.zeros(8, np.float32)
+    for i in range(9):
+        fwd = xu.add32(fwd, d[i])
+        rev = xu.add32(rev, d[8 - i])
+    assert np.array_equal(ref[0, 2, 2], fwd) and not np.array_equal(fwd, rev)
+
+
+def test_nhwc_wrong_rules_are_told_apart():
+    """The >= 0 ReLU decision and an unrounded residual BN differ from the
+    correct rule on the inputs the GPU tests use."""
+    g = torch.Generator().manual_seed(7)
+    d = xn.int_bn_bwd_inputs(300, 16, g)
+    sc, sh = xn.coef_from_save(d["save"], d["w"], d["b"])
+    gt, ge = xn.relu_mask(2, d["x"], sc, sh), xn.relu_mask(2, d["x"], sc, sh, positive="ge")
+    assert (gt != ge).any() and not (gt & ~ge).any()
+    sg, _ = xn.bn_bwd_sums(xb.cpu64(d["dy"]) * torch.from_numpy(gt), d["x"], d["save"], exact_regime=True)
+    sw, _ = xn.bn_bwd_sums(xb.cpu64(d["dy"]) * torch.from_numpy(ge), d["x"], d["save"])
+    assert not torch.equal(sg, sw)
+    x, res = torch.randn(300, 16, generator=g).bfloat16(), torch.randn(300, 16, generator=g).bfloat16()
+    one = np.ones(16, np.float32)
+    rsc, rsh = (torch.randn(16, generator=g).numpy() for _ in range(2))
+    a = xn.bn_fwd_ref(x, one, 0 * one, True, res, rsc, rsh)
+    bnr = xn.bn_fwd_ref(x, one, 0 * one, True, res, rsc, rsh, round_res=False)
+    assert not np.array_equal(a, bnr)
+    # mask bits: bit k of byte (m, j) is channel 8 j + k
+    y = np.zeros((2, 16), np.float32)
+    y[1, 9] = 2.0
+    assert xn.mask_bits_ref(y).tolist() == [[0, 0], [0, 2]] and xn.unpack_bits(xn.mask_bits_ref(y), 16)[1, 9]
+
+
+def test_nhwc_bounds_reject_a_dropped_row_and_a_swapped_tap():
+    """A plain fp32 evaluation of dx stays inside the derived bound; the same
+    with one row left out of the sums' input, or the statistics of M - 1 rows,
+    does not.  The stem unpack index with its parity bits exchanged moves taps."""
+    g = torch.Generator().manual_seed(11)
+    M, Cc = 333, 16
+    x, dy = torch.randn(M, Cc, generator=g).bfloat16(), torch.randn(M, Cc, generator=g).bfloat16()
+    w = torch.randn(Cc, generator=g)
+    s = xn.bn_stats64(x) / M
+    save = torch.cat([s[0], (s[1] - s[0] ** 2 + 1e-3).rsqrt()]).float()
+    sums, sabs = xn.bn_bwd_sums(dy, x, save)
+    acc32 = torch.stack([dy.float().sum(0), (dy.float() * ((x.float() - save[:Cc]) * save[Cc:])).sum(0)])
+    bound = xn.bwd_sums_bound(M, sabs)
+    assert bool(((acc32.double() - sums).abs() <= bound).all())
+    dropped = xn.bn_bwd_sums(dy[:-1], x[:-1], save)[0]
+    assert bool(((dropped - sums).abs() > bound).any())
+    ref, E = xn.bn_dx64(dy, x, save, w, acc32, M)
+    a = w * save[Cc:]
+    got = (a * (dy.float() - acc32[0] / M - (x.float() - save[:Cc]) * save[Cc:] * (acc32[1] / M))).bfloat16()
+    xb.assert_within(got, ref, xn.bf16_bound(ref, E), "fp32 dx")
+    with pytest.raises(AssertionError):
+        xb.assert_within(got[torch.randperm(M, generator=g)], ref, xn.bf16_bound(ref, E), "permuted rows")
+    # statistics: exact sums of M rows vs M - 1 rows
+    xi = exact.int_bf16((M, Cc), -4, 4, generator=g)
+    with pytest.raises(AssertionError):
+        exact.assert_exact(xn.bn_stats64(xi[:-1]).float(), xn.bn_stats_exact(xi), "a dropped row")
+    # the swapped stem tap
+    k, kw = xn.stem_unpack_index(), xn.stem_unpack_index(swap_parity=True)
+    assert len(set(k.reshape(-1).tolist())) == 147 and (k != kw).any()
+    slab = torch.arange(2 * 256).reshape(1, 2, 256).float()
+    dw0 = torch.zeros(2, 3, 7, 7)
+    assert not np.array_equal(xn.stem_unpack_ref(slab, dw0), xn.stem_unpack_ref(slab, dw0, swap_parity=True))
+    # ... and the layouts invert each other: packing a 7x7 weight and reading it back through the unpack index
+    w7 = torch.randn(2, 3, 7, 7, generator=g).bfloat16()
+    assert np.array_equal(xn.stem_pack_ref(w7).reshape(2, 256)[:, k], xn.np32(w7))
+
+
+def test_nhwc_geometry_model_and_layout_references():
+    """bn_loops on hand-worked shapes (C = 64: RPI = 32), s2d against a direct
+    loop, phase blocks against the documented taps."""
+    assert xn.bn_geom(1, 64) == {"CVB": 8, "RPI": 32, "rpb": 32, "rb": 1, "groups": 1}
+    assert xn.bn_loops(1, 64) == {"rem_only", "idle", "small"}
+    assert xn.bn_loops(4 * 32 + 1, 64) == {"u+1", "idle"}
+    assert xn.bn_loops(16 * 32 + 5, 64) == {"u+1", "u+3", "idle", "blocks"}
+    assert xn.bn_geom(16 * 32 + 5, 64)["rpb"] == 9 * 32 and "groups" in xn.bn_loops(8, 512)
+    g = torch.Generator().manual_seed(2)
+    x = torch.randn(1, 5, 6, 3, generator=g).bfloat16()
+    S = xn.s2d_ref(x, 6, 6, 3)
+    for i, j, a, b, c in [(0, 0, 0, 0, 0), (1, 1, 1, 1, 2), (2, 3, 1, 0, 1), (3, 4, 0, 1, 0), (5, 5, 1, 1, 1)]:
+        yy, xx = 2 * i + a - 3, 2 * j + b - 3
+        want = float(x[0, yy, xx, c]) if 0 <= yy < 5 and 0 <= xx < 6 else 0.0
+        assert float(S[0, i, j, (a * 2 + b) * 3 + c]) == want
+    wt = torch.arange(2 * 9 * 8).reshape(2, 3, 3, 8).float()
+    ph = xn.phase_ref(wt)
+    assert ph[:8].tolist() == wt[0, 1, 1].tolist() and ph[2 * 8 + 8:2 * 8 + 16].tolist() == wt[0, 1, 2].tolist()
+    assert ph.size == 9 * 2 * 8
+    h = torch.randn(2, 50, 8, generator=g).bfloat16()
+    f = xn.head_pool_ref(h)
+    assert float(np.abs(f - xn.np32(h).astype(np.float64).mean(1)).max()) < 2.0 ** -8
+
+
+def test_nhwc_out_row_corrections():
+    """Which image sizes make out_row's float-reciprocal divisions come out one
+    too small (plain fp32 arithmetic): the GPU tests rely on 5 x 11 and 3 x 41."""
+    assert xn.out_row_corrections(5, 11, 165) == (True, False)
+    assert xn.out_row_corrections(3, 41, 246) == (True, True)
+    for H, W in ((1, 1), (3, 5), (7, 7), (13, 9), (56, 56)):
+        assert xn.out_row_corrections(H, W, 4 * H * W) == (False, False)
+    assert xn.out_row_corrections(57, 59, 4988 * 57 * 59) == (False, False)
