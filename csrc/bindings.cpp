@@ -13,9 +13,10 @@ using namespace dl;
 PYBIND11_MODULE(_C, m) {
   m.doc() = "distlearn MI355X (gfx950) native kernels, RCCL communicator and data runtime";
 
-  // per-call values, opaque to Python: built by side_sgd_job / side_reduce_job / next_prep
+  // per-call values, opaque to Python: built by side_sgd_job / side_reduce_job / next_prep / augment
   py::class_<SideJob>(m, "SideJob");
   py::class_<NextPrep>(m, "NextPrep");
+  py::class_<Augment>(m, "Augment");
 
   // ---- flat bucket kernels --------------------------------------------------
   m.def("sgd_update", &sgd_update, py::arg("p"), py::arg("g"), py::arg("mom"), py::arg("p16"), py::arg("slot"),
@@ -39,7 +40,11 @@ PYBIND11_MODULE(_C, m) {
         py::arg("lens"), py::arg("slabs"), py::arg("splits"), py::arg("tail"), py::arg("tail_slab"),
         py::arg("skip_lo"), py::arg("skip_hi"), py::arg("stream"), py::arg("lr_dev") = 0,
         py::arg("next_prep") = py::none());
-  m.def("next_prep", &next_prep);
+  m.def("next_prep", &next_prep, py::arg("img"), py::arg("order"), py::arg("lab_all"), py::arg("lab_out"),
+        py::arg("ctr"), py::arg("n_order"), py::arg("B"), py::arg("C"), py::arg("mean"), py::arg("std"), py::arg("xp"),
+        py::arg("Cp"), py::arg("H"), py::arg("W"), py::arg("sp"), py::arg("zp"), py::arg("zn"), py::arg("w1p"),
+        py::arg("w1_cp"), py::arg("pack_off"), py::arg("pack_len"), py::arg("augment") = py::none());
+  m.def("augment", &augment, py::arg("params"), py::arg("pad"), py::arg("flip"), py::arg("n_samples"));
   m.def("side_sgd_job", &side_sgd_job, py::arg("p"), py::arg("g"), py::arg("mom"), py::arg("p16"), py::arg("slot"),
         py::arg("lr"), py::arg("momentum"), py::arg("wd"), py::arg("lo"), py::arg("hi"), py::arg("offs"),
         py::arg("lens"), py::arg("slabs"), py::arg("splits"), py::arg("nblk"), py::arg("lr_dev") = 0);
@@ -127,7 +132,12 @@ PYBIND11_MODULE(_C, m) {
   m.def("pack_weight", &pack_weight);
   m.def("pad_channels", &pad_channels);
   m.def("prep_step", &prep_step);
-  m.def("prep_step_gather", &prep_step_gather);
+  m.def("prep_step_gather", &prep_step_gather, py::arg("img"), py::arg("order"), py::arg("lab_all"),
+        py::arg("lab_out"), py::arg("ctr"), py::arg("n_order"), py::arg("B"), py::arg("C"), py::arg("mean"),
+        py::arg("std"), py::arg("xp"), py::arg("Cp"), py::arg("H"), py::arg("W"), py::arg("sp"), py::arg("w1"),
+        py::arg("w1p"), py::arg("w1_cout"), py::arg("taps"), py::arg("w1_c"), py::arg("w1_cp"), py::arg("tw"),
+        py::arg("twt"), py::arg("tcout"), py::arg("tcin"), py::arg("zp"), py::arg("zn"), py::arg("stream"),
+        py::arg("augment") = py::none());
   m.def("bn_finalize", &bn_finalize);
   m.def("bn_relu_pool_fwd", &bn_relu_pool_fwd);
   m.def("bn_bwd_blocks", &bn_bwd_blocks);

@@ -59,6 +59,18 @@ void sgd_update_g16(uintptr_t p, uintptr_t g16, uintptr_t mom, uintptr_t p16, ui
 // accumulators (prep_dev.h) and writes the first layer's updated weights into the
 // packed bf16 operand w1p (from the slab tail, or from the main loop's elements
 // [pack_off, +pack_len)).  Checked when next_prep builds it; never modified after.
+// Augmentation of a device-side gather (prep_step_gather, next_prep): random
+// crop after zero padding by `pad` (0..8) and horizontal flip (flip 1), drawn per
+// sample from a counter-based hash of the device int64 pair params = {seed,
+// base} and the step counter (prep_dev.h augment_draw).  n_samples: images in the
+// dataset the gather reads (the bound of its realigned loads).  Checked when
+// augment builds it (pad < min(H, W) at use); never modified after.
+struct Augment {
+  const uintptr_t params;
+  const int pad, flip;
+  const int64_t n_samples;
+};
+Augment augment(uintptr_t params, int pad, int flip, int64_t n_samples);
 struct NextPrep {
   const uintptr_t img, order, lab_all, lab_out, ctr;
   const int n_order, B, C;
@@ -70,11 +82,14 @@ struct NextPrep {
   const uintptr_t w1p;
   const int w1_cp;
   const int64_t pack_off, pack_len;
+  const uintptr_t aug_params;  // 0: no augmentation
+  const int aug_pad, aug_flip;
+  const int64_t aug_n;
 };
 NextPrep next_prep(uintptr_t img, uintptr_t order, uintptr_t lab_all, uintptr_t lab_out, uintptr_t ctr, int n_order,
                    int B, int C, std::vector<float> mean, std::vector<float> stdv, uintptr_t xp, int Cp, int H, int W,
                    int sp, std::vector<uintptr_t> zp, std::vector<int64_t> zn, uintptr_t w1p, int w1_cp,
-                   int64_t pack_off, int64_t pack_len);
+                   int64_t pack_off, int64_t pack_len, const Augment* aug = nullptr);
 void sgd_update_slabs(uintptr_t p, uintptr_t g, uintptr_t mom, uintptr_t p16, uintptr_t slot, float lr,
                       float momentum, float wd, int64_t n, std::vector<int64_t> offs, std::vector<int64_t> lens,
                       std::vector<uintptr_t> slabs, std::vector<int> splits, std::vector<int64_t> tail,
@@ -196,7 +211,8 @@ void prep_step_gather(uintptr_t img, uintptr_t order, uintptr_t lab_all, uintptr
                       int n_order, int B, int C, std::vector<float> mean, std::vector<float> stdv, uintptr_t xp,
                       int Cp, int H, int W, int sp, uintptr_t w1, uintptr_t w1p, int w1_cout, int taps, int w1_c,
                       int w1_cp, std::vector<uintptr_t> tw, std::vector<uintptr_t> twt, std::vector<int> tcout,
-                      std::vector<int> tcin, std::vector<uintptr_t> zp, std::vector<int64_t> zn, uintptr_t stream);
+                      std::vector<int> tcin, std::vector<uintptr_t> zp, std::vector<int64_t> zn, uintptr_t stream,
+                      const Augment* aug = nullptr);
 
 // bn_pool.hip -----------------------------------------------------------------
 void bn_finalize(uintptr_t partial, int T, int C, int64_t M, uintptr_t gamma, uintptr_t beta, uintptr_t bias,

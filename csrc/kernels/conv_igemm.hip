@@ -77,19 +77,32 @@ void prep_step(uintptr_t x, uintptr_t xp, int64_t P, int C, int Cp, int H, int W
   launch_prep(a, P, w1, w1p, w1_cout, taps, w1_c, w1_cp, tw, twt, tcout, tcin, zp, zn, stream);
 }
 
+// The augmentation value of a gather; every check that needs no image runs here.
+Augment augment(uintptr_t params, int pad, int flip, int64_t n_samples) {
+  if (!params) throw std::runtime_error("augment: null parameter pointer");
+  if (params % 8) throw std::runtime_error("augment: the parameters are two aligned int64");
+  if (pad < 0 || pad > 8) throw std::runtime_error("augment: pad must be 0..8");
+  if (flip != 0 && flip != 1) throw std::runtime_error("augment: flip must be 0 or 1");
+  if (n_samples <= 0) throw std::runtime_error("augment: the dataset's sample count must be positive");
+  return Augment{params, pad, flip, n_samples};
+}
+
 // Same launch with the step's input gathered on the device: batch b of step
 // s (= ctr[0]) is sample order[(s*B + b) mod n_order] of the uint8 NHWC
 // dataset `img`, normalised ((v/255 - mean)/std), channel- and spatially
 // padded into xp; its label goes to lab_out[b].  head_wgrad advances ctr[0]
-// later in the step, so a captured graph replays consecutive batches.
+// later in the step, so a captured graph replays consecutive batches.  aug:
+// random crop / flip of each gathered image (dl_ops.h Augment; null: none).
 void prep_step_gather(uintptr_t img, uintptr_t order, uintptr_t lab_all, uintptr_t lab_out, uintptr_t ctr,
                       int n_order, int B, int C, std::vector<float> mean, std::vector<float> stdv, uintptr_t xp,
                       int Cp, int H, int W, int sp, uintptr_t w1, uintptr_t w1p, int w1_cout, int taps, int w1_c,
                       int w1_cp, std::vector<uintptr_t> tw, std::vector<uintptr_t> twt, std::vector<int> tcout,
-                      std::vector<int> tcin, std::vector<uintptr_t> zp, std::vector<int64_t> zn, uintptr_t stream) {
+                      std::vector<int> tcin, std::vector<uintptr_t> zp, std::vector<int64_t> zn, uintptr_t stream,
+                      const Augment* aug) {
   PrepArgs a{};
   a.xp = (bf16_t*)xp; a.C = C; a.Cp = Cp; a.H = H; a.W = W; a.sp = sp;
   prep_set_gather(a, img, order, lab_all, lab_out, ctr, n_order, B, C, mean, stdv);
+  if (aug) prep_set_augment(a, aug->params, aug->pad, aug->flip, aug->n_samples);
   launch_prep(a, (int64_t)B * H * W, w1, w1p, w1_cout, taps, w1_c, w1_cp, tw, twt, tcout, tcin, zp, zn, stream);
 }
 

@@ -279,6 +279,7 @@ static PrepArgs next_prep_args(const NextPrep& n) {
   PrepArgs a{};
   a.xp = (bf16_t*)n.xp; a.C = n.C; a.Cp = n.Cp; a.H = n.H; a.W = n.W; a.sp = n.sp;
   prep_set_gather(a, n.img, n.order, n.lab_all, n.lab_out, n.ctr, n.n_order, n.B, n.C, n.mean, n.stdv);
+  if (n.aug_params) prep_set_augment(a, n.aug_params, n.aug_pad, n.aug_flip, n.aug_n);
   prep_set_pad(a, (int64_t)n.B * n.H * n.W);
   prep_set_zero(a, n.zp, n.zn);
   return a;
@@ -291,9 +292,10 @@ static PrepArgs next_prep_args(const NextPrep& n) {
 NextPrep next_prep(uintptr_t img, uintptr_t order, uintptr_t lab_all, uintptr_t lab_out, uintptr_t ctr, int n_order,
                    int B, int C, std::vector<float> mean, std::vector<float> stdv, uintptr_t xp, int Cp, int H, int W,
                    int sp, std::vector<uintptr_t> zp, std::vector<int64_t> zn, uintptr_t w1p, int w1_cp,
-                   int64_t pack_off, int64_t pack_len) {
+                   int64_t pack_off, int64_t pack_len, const Augment* aug) {
   const NextPrep n{img, order, lab_all, lab_out, ctr, n_order, B,   C,     mean,     stdv,    xp,
-                   Cp,  H,     W,       sp,      zp,  zn,      w1p, w1_cp, pack_off, pack_len};
+                   Cp,  H,     W,       sp,      zp,  zn,      w1p, w1_cp, pack_off, pack_len,
+                   aug ? aug->params : 0, aug ? aug->pad : 0, aug ? aug->flip : 0, aug ? aug->n_samples : 0};
   next_prep_args(n);
   return n;
 }

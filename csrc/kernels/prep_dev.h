@@ -31,10 +31,132 @@ struct PrepArgs {
   int nz, nb_zero;
   float* zp[8];
   int zn4[8];
+  // augmentation of the gathered batch (aug != nullptr; prep_pad_block_aug):
+  // aug = device {seed, base}, pad = crop shift range, n_samples = images in img
+  const unsigned long long* aug;
+  int pad, flip;
+  int64_t n_samples;
 };
+
+// Crop / flip parameters of draw idx: z = splitmix64's output for the state
+// seed + (idx + 1) * golden; flip = bit 0, dx / dy = bits 8..23 / 32..47 mod
+// (2 pad + 1).  Python's augment_params (torch_distlearn_amd/data) is the
+// same formula; all arithmetic wraps at 64 bits.
+__device__ __forceinline__ void augment_draw(unsigned long long seed, unsigned long long idx, int pad, int flip_on,
+                                             int& flip, int& dx, int& dy) {
+  unsigned long long z = seed + (idx + 1ull) * 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  const unsigned span = 2u * (unsigned)pad + 1u;
+  flip = flip_on ? (int)(z & 1ull) : 0;
+  dx = (int)(((unsigned)(z >> 8) & 0xffffu) % span);
+  dy = (int)(((unsigned)(z >> 32) & 0xffffu) % span);
+}
+
+// The augmented gather (a.img and a.aug set): output pixel (h, w) of batch row
+// b is source pixel (h + dy - pad, (flip ? W-1-w : w) + dx - pad) of its stored
+// image, normalised by the expression of prep_pad_block, or exactly zero in
+// every channel when that position lies outside the image.  Reads stay inside
+// [img, img + n_samples*H*W*C); writes stay inside the interior of xp.
+__device__ __forceinline__ void prep_pad_block_aug(const PrepArgs& a, int blk) {
+  const int HW = a.H * a.W, Hp = a.H + 2 * a.sp, Wp = a.W + 2 * a.sp;
+  const unsigned long long step = *a.ctr;  // advanced by head_wgrad later in the step
+  const unsigned long long seed = a.aug[0], draw0 = (a.aug[1] + step) * (unsigned long long)a.B;
+  if (a.quad) {
+    // block = one image (one draw, so flip / dx / dy are uniform), thread = 4
+    // consecutive output pixels of one row = 4 consecutive source pixels
+    // (reversed under flip): 12 bytes at any byte alignment
+    const int b = blk;
+    const int pos = (int)((step * (unsigned long long)a.B + (unsigned long long)b) % (unsigned)a.n_order);
+    const int smp = a.order[pos];
+    if (threadIdx.x == 0) a.lab_out[b] = a.lab_all[smp];
+    int flip, dx, dy;
+    augment_draw(seed, draw0 + (unsigned long long)b, a.pad, a.flip, flip, dx, dy);
+    const int64_t last = a.n_samples * HW * 3 - 4;  // byte offset of the dataset's last dword (H*W*3 % 4 == 0)
+    for (int q4 = threadIdx.x; q4 < HW / 4; q4 += 256) {
+      const int r = q4 * 4, h = r / a.W, w = r - h * a.W;
+      const int hs = h + dy - a.pad;
+      const int c0 = (flip ? a.W - 4 - w : w) + dx - a.pad;  // source column of the thread's first source pixel
+      uint32_t o[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};      // 4 output pixels x 2 words (3 bf16 + a zero)
+      if (hs >= 0 && hs < a.H && c0 > -4 && c0 < a.W) {
+        // the aligned dwords covering the 12 bytes, each clamped into the
+        // dataset: a clamped dword only ever feeds pixels that are out of range
+        const int64_t byte0 = ((int64_t)smp * HW + (int64_t)hs * a.W + c0) * 3;
+        const int64_t al = byte0 & ~(int64_t)3;
+        const int sh = 8 * (int)(byte0 & 3);
+        uint32_t d[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int64_t off = al + 4 * k;
+          d[k] = *reinterpret_cast<const uint32_t*>(a.img + (off < 0 ? 0 : (off > last ? last : off)));
+        }
+        uint32_t e[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          e[k] = (uint32_t)(((((unsigned long long)d[k + 1]) << 32) | (unsigned long long)d[k]) >> sh);
+        float f[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) {
+          const float u = (float)((e[k >> 2] >> (8 * (k & 3))) & 0xffu);
+          f[k] = (u * (1.0f / 255.0f) - a.mean[k % 3]) * a.inv_std[k % 3];
+        }
+#pragma unroll
+        for (int px = 0; px < 4; ++px) {  // output pixel px = source pixel j (static indices: no scratch)
+          const int j = 3 - px;
+          const float f0 = flip ? f[3 * j] : f[3 * px], f1 = flip ? f[3 * j + 1] : f[3 * px + 1];
+          const float f2 = flip ? f[3 * j + 2] : f[3 * px + 2];
+          const int col = c0 + (flip ? j : px);
+          const bool in = col >= 0 && col < a.W;
+          o[2 * px] = in ? pack_bf16x2(f0, f1) : 0u;
+          o[2 * px + 1] = in ? pack_bf16x2(f2, 0.f) : 0u;
+        }
+      }
+      if (a.Cp == 4) {
+        uint2* dst = reinterpret_cast<uint2*>(a.xp + (((int64_t)b * Hp + h + a.sp) * Wp + w + a.sp) * 4);
+#pragma unroll
+        for (int px = 0; px < 4; ++px) dst[px] = make_uint2(o[2 * px], o[2 * px + 1]);
+      } else {
+        uint4* dst = reinterpret_cast<uint4*>(a.xp + (((int64_t)b * Hp + h + a.sp) * Wp + w + a.sp) * 8);
+#pragma unroll
+        for (int px = 0; px < 4; ++px) dst[px] = make_uint4(o[2 * px], o[2 * px + 1], 0u, 0u);
+      }
+    }
+    return;
+  }
+  for (int p = blk * 256 + threadIdx.x; p < a.P; p += a.nb_pad * 256) {
+    const int b = p / HW;
+    const int r = p - b * HW, h = r / a.W, w = r - h * a.W;
+    const int pos = (int)((step * (unsigned long long)a.B + (unsigned long long)b) % (unsigned)a.n_order);
+    const int smp = a.order[pos];
+    int flip, dx, dy;
+    augment_draw(seed, draw0 + (unsigned long long)b, a.pad, a.flip, flip, dx, dy);
+    const int hs = h + dy - a.pad, ws = (flip ? a.W - 1 - w : w) + dx - a.pad;
+    float f0 = 0.f, f1 = 0.f, f2 = 0.f;  // named, not an indexed array: registers, no scratch
+    if (hs >= 0 && hs < a.H && ws >= 0 && ws < a.W && smp >= 0 && smp < a.n_samples) {
+      const uint8_t* src = a.img + ((int64_t)smp * HW + hs * a.W + ws) * a.C;
+      f0 = (src[0] * (1.0f / 255.0f) - a.mean[0]) * a.inv_std[0];
+      if (a.C > 1) f1 = (src[1] * (1.0f / 255.0f) - a.mean[1]) * a.inv_std[1];
+      if (a.C > 2) f2 = (src[2] * (1.0f / 255.0f) - a.mean[2]) * a.inv_std[2];
+    }
+    if (r == 0) a.lab_out[b] = a.lab_all[smp];
+    const uint32_t w0 = pack_bf16x2(f0, f1), w1 = pack_bf16x2(f2, 0.f);  // +0.0f packs to the bits 0
+    const int64_t q = ((int64_t)b * Hp + h + a.sp) * Wp + w + a.sp;  // interior of the zero-bordered buffer
+    if (a.Cp == 4) {
+      *reinterpret_cast<uint2*>(a.xp + q * 4) = make_uint2(w0, w1);
+    } else {  // Cp 8 or 16 (prep_set_pad)
+      *reinterpret_cast<uint4*>(a.xp + q * a.Cp) = make_uint4(w0, w1, 0u, 0u);
+      if (a.Cp > 8) *reinterpret_cast<uint4*>(a.xp + q * a.Cp + 8) = make_uint4(0u, 0u, 0u, 0u);
+    }
+  }
+}
 
 // Workgroup blk (< nb_pad) of the pad/gather job.
 __device__ __forceinline__ void prep_pad_block(const PrepArgs& a, int blk) {
+  if (a.aug) {  // kernel argument: uniform over the launch
+    prep_pad_block_aug(a, blk);
+    return;
+  }
   if (a.quad) {
     // fast path (3 -> 8 channels, W % 4 == 0): block = one image, thread =
     // 4 consecutive pixels of one row; every load of a thread is issued
@@ -163,6 +285,18 @@ inline void prep_set_gather(PrepArgs& a, uintptr_t img, uintptr_t order, uintptr
     a.mean[c] = c < C ? mean[c] : 0.f;
     a.inv_std[c] = c < C ? 1.0f / stdv[c] : 1.f;
   }
+}
+
+// Host: the augmentation of a gather (after prep_set_gather, with a.H / a.W
+// set).  params = device int64 {seed, base}; the value's own checks ran in
+// augment() (conv_igemm.hip), those against the image run here.
+inline void prep_set_augment(PrepArgs& a, uintptr_t params, int pad, int flip, int64_t n_samples) {
+  if (!a.img) throw std::runtime_error("augment: only the device-side gather can be augmented");
+  if (!params || params % 8 || pad < 0 || pad > 8 || (flip != 0 && flip != 1) || n_samples <= 0)
+    throw std::runtime_error("augment: bad value");
+  if (pad >= std::min(a.H, a.W)) throw std::runtime_error("augment: pad must be smaller than the image");
+  if ((uintptr_t)a.img % 4) throw std::runtime_error("augment: the dataset must be 4-byte aligned");
+  a.aug = (const unsigned long long*)params; a.pad = pad; a.flip = flip; a.n_samples = n_samples;
 }
 
 }  // namespace dl

@@ -39,8 +39,8 @@ from torch_distlearn_amd import LocalhostTree  # noqa: E402
 from torch_distlearn_amd.checkpoint import results_dir, resume_trainer, save_trainer  # noqa: E402
 from torch_distlearn_amd.data import Dataset, DeviceEvalLoader, DeviceLoader  # noqa: E402
 from torch_distlearn_amd.engine import DataParallelTrainer  # noqa: E402
-from torch_distlearn_amd.launch import (add_checkpoint_flags, add_node_flags, add_schedule_flags,  # noqa: E402
-                                        device_of, node_opts, quiet_unless_root)
+from torch_distlearn_amd.launch import (add_augment_flag, add_checkpoint_flags, add_node_flags,  # noqa: E402
+                                        add_schedule_flags, augment_of, device_of, node_opts, quiet_unless_root)
 from torch_distlearn_amd import schedules  # noqa: E402
 from torch_distlearn_amd.models import CifarConvNet  # noqa: E402
 from torch_distlearn_amd.utils.metrics import ConfusionMatrix, JsonlMetrics  # noqa: E402
@@ -65,6 +65,7 @@ def main():
                          "on the HIP fast path)")
     add_checkpoint_flags(ap)
     add_schedule_flags(ap)
+    add_augment_flag(ap)
     opt = ap.parse_args()
     node_opts(opt)
     dev = device_of(opt)
@@ -80,8 +81,10 @@ def main():
     backend = opt.backend if dev.type == "cuda" else "torch"
     graph = bool(opt.graph) and dev.type == "cuda"
     fast = backend == "hip" and graph  # bench.py's path: device sampler + unrolled graph replays
+    aug = augment_of(opt, fast)
+    print(f"augment: {opt.augment}")
     if fast:
-        train_b = DeviceLoader(train, "label-uniform", per_node, seed=opt.seed + opt.nodeIndex)
+        train_b = DeviceLoader(train, "label-uniform", per_node, seed=opt.seed + opt.nodeIndex, augment=aug)
     else:
         train_b = train.sampledBatcher("label-uniform", per_node, dtype=dt, seed=opt.seed + opt.nodeIndex)
     test_b = test.sampledBatcher("linear", per_node, dtype=dt)

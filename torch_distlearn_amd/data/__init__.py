@@ -28,6 +28,7 @@ deterministic data of the same shapes.
 from __future__ import annotations
 
 import os
+from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -195,6 +196,52 @@ class Batcher:
     get_batch = getBatch
 
 
+_M64 = (1 << 64) - 1
+
+
+def _mix64(z: int) -> int:
+    """The output function of splitmix64 (unsigned 64-bit, wrapping)."""
+    z &= _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def augment_params(seed: int, idx: int, pad: int, flip: bool = True) -> Tuple[int, int, int]:
+    """``(flip, dx, dy)`` of draw ``idx`` (= global batch count * B + row):
+    the reference of the gather kernel's counter-based hash (csrc/kernels/
+    prep_dev.h augment_draw), bit for bit.  Output pixel (h, w) of the sample
+    is source pixel ``(h + dy - pad, (W-1-w if flip else w) + dx - pad)``."""
+    z = _mix64(int(seed) + (int(idx) + 1) * 0x9E3779B97F4A7C15)
+    span = 2 * int(pad) + 1
+    return (int(z & 1) if flip else 0), ((z >> 8) & 0xFFFF) % span, ((z >> 32) & 0xFFFF) % span
+
+
+@dataclass(frozen=True)
+class Augment:
+    """Random crop after zero padding by ``pad`` pixels (0: none) and random
+    horizontal flip of every training sample drawn by a :class:`DeviceLoader`.
+    ``seed`` None: derived from the loader's seed and the dataset partition."""
+    pad: int = 4
+    flip: bool = True
+    seed: Optional[int] = None
+
+    def __post_init__(self):
+        if not 0 <= int(self.pad) <= 8:
+            raise ValueError("Augment: pad must be 0..8")
+
+
+AUGMENT_CHOICES = {"none": None, "flip": Augment(pad=0, flip=True), "crop4": Augment(pad=4, flip=False),
+                   "crop4flip": Augment(pad=4, flip=True)}
+
+
+def augment_from_name(name: str) -> Optional[Augment]:
+    """``none | flip | crop4 | crop4flip`` (the examples' ``--augment``)."""
+    if name not in AUGMENT_CHOICES:
+        raise ValueError(f"unknown augmentation {name!r}: one of {', '.join(AUGMENT_CHOICES)}")
+    return AUGMENT_CHOICES[name]
+
+
 class DeviceLoader:
     """Device-side batching for graph-captured training steps.
 
@@ -214,11 +261,28 @@ class DeviceLoader:
 
     Paths without the native executor call :meth:`getBatch` (eager gather of
     the same batch sequence).
+
+    ``augment`` (:class:`Augment`): random crop / flip inside that gather,
+    drawn per sample from a counter-based hash (:func:`augment_params`) of the
+    seed and the global draw count -- ``aug`` holds ``[seed, base]`` on the
+    device with ``base + ctr[0] == drawn``, so captured graphs stay valid and
+    :meth:`skip` continues the stream of a resumed run; :meth:`getBatch`
+    applies the same augmentation with torch ops.  None: no augmentation.
     """
 
-    def __init__(self, ds: PartitionedDataset, kind: str = "permutation", batch: int = 32, seed: int = 0):
+    def __init__(self, ds: PartitionedDataset, kind: str = "permutation", batch: int = 32, seed: int = 0,
+                 augment: Optional[Augment] = None):
         self.ds, self.batch = ds, int(batch)
         self.H, self.W = ds.H, ds.W
+        self.augment = augment
+        self.aug = None  # device int64 [seed, base]: base + ctr[0] = drawn (a captured graph reads it each replay)
+        if augment is not None:
+            if int(augment.pad) >= min(ds.H, ds.W):
+                raise ValueError("Augment: pad must be smaller than the image")
+            s = augment.seed if augment.seed is not None else _mix64(int(seed) * 0x9E3779B97F4A7C15 + ds.partition)
+            self.aug_seed = int(s) & _M64
+            signed = self.aug_seed - (1 << 64) if self.aug_seed >> 63 else self.aug_seed
+            self.aug = torch.tensor([signed, 0], dtype=torch.int64, device=ds.device)
         self.sampler = make_sampler(ds.N, ds.labels_host.tolist() if kind == "label-uniform" else None,
                                     ds.num_classes, ds.partition, ds.partitions, kind, seed)
         self.steps_per_epoch = max(1, int(self.sampler.size()) // self.batch)
@@ -279,6 +343,31 @@ class DeviceLoader:
             self._next_epoch()
         self._host_steps += n
         self.ctr[0] = (self.epoch % 2) * self.steps_per_epoch + self._host_steps
+        if self.aug is not None:  # the augmentation stream continues at the global draw count
+            self.aug[1] = self.drawn - ((self.epoch % 2) * self.steps_per_epoch + self._host_steps)
+
+    def augment_args(self):
+        """The native ``Augment`` value of this loader's gather (``prep_step_gather`` /
+        ``next_prep``), or None without augmentation."""
+        if self.augment is None:
+            return None
+        return native().augment(self.aug.data_ptr(), int(self.augment.pad), int(bool(self.augment.flip)),
+                                int(self.ds.N))
+
+    def _augment(self, x: torch.Tensor, draw: int) -> torch.Tensor:
+        """The augmentation of batch number ``draw`` applied to its gathered,
+        normalised images x [B, H, W, C] with torch ops (augment_params)."""
+        B, H, W = x.shape[0], x.shape[1], x.shape[2]
+        pad = int(self.augment.pad)
+        prm = [augment_params(self.aug_seed, draw * self.batch + b, pad, bool(self.augment.flip)) for b in range(B)]
+        flip, dx, dy = (torch.tensor(v, dtype=torch.int64, device=x.device) for v in zip(*prm))
+        ar_h, ar_w = torch.arange(H, device=x.device), torch.arange(W, device=x.device)
+        hs = ar_h[None, :] + (dy[:, None] - pad)
+        ws = torch.where(flip[:, None] == 1, W - 1 - ar_w[None, :], ar_w[None, :]) + (dx[:, None] - pad)
+        inside = ((hs >= 0) & (hs < H))[:, :, None] & ((ws >= 0) & (ws < W))[:, None, :]
+        rows = torch.arange(B, device=x.device)[:, None, None]
+        g = x[rows, hs.clamp(0, H - 1)[:, :, None], ws.clamp(0, W - 1)[:, None, :]]
+        return torch.where(inside[..., None], g, torch.zeros((), dtype=x.dtype, device=x.device))
 
     def gather_args(self):
         ds = self.ds
@@ -304,6 +393,8 @@ class DeviceLoader:
         mean = torch.tensor(ds.mean[:ds.C], dtype=torch.float32, device=x.device)
         std = torch.tensor(ds.std[:ds.C], dtype=torch.float32, device=x.device)
         x = ((x - mean) / std)
+        if self.augment is not None:
+            x = self._augment(x, int(self.aug[1].item()) + int(self.ctr[0].item()))
         self.ctr[0] += 1
         y = ds.labels.index_select(0, idx)
         self.labels_out.copy_(y)
@@ -462,5 +553,6 @@ def Dataset(name: str = "cifar10", partition: int = 1, partitions: int = 1, trai
     raise ValueError(f"unknown dataset {name!r}")
 
 
-__all__ = ["Dataset", "PartitionedDataset", "Batcher", "make_sampler", "synthetic_cifar10", "synthetic_mnist",
+__all__ = ["Dataset", "PartitionedDataset", "Batcher", "DeviceLoader", "DeviceEvalLoader", "Augment", "augment_params",
+           "augment_from_name", "make_sampler", "synthetic_cifar10", "synthetic_mnist",
            "load_cifar10", "load_mnist", "SAMPLERS"]

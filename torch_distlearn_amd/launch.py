@@ -74,6 +74,26 @@ def add_schedule_flags(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
     return ap
 
 
+def add_augment_flag(ap: argparse.ArgumentParser) -> argparse.ArgumentParser:
+    """``--augment``: random crop (after 4 pixels of zero padding) and / or
+    horizontal flip of the training samples, inside the device-side gather."""
+    ap.add_argument("--augment", default="none", choices=["none", "flip", "crop4", "crop4flip"],
+                    help="training-set augmentation (device data path only)")
+    return ap
+
+
+def augment_of(opt, device_loader: bool):
+    """The ``augment=`` of a DeviceLoader for ``--augment`` (None: off).  The
+    host Batcher path has no augmentation: anything but ``none`` is an error."""
+    from .data import augment_from_name
+
+    aug = augment_from_name(getattr(opt, "augment", "none"))
+    if aug is not None and not device_loader:
+        raise SystemExit(f"--augment {opt.augment} needs the device data path (--cuda --backend hip --graph 1): "
+                         "the host Batcher does not augment; use --augment none")
+    return aug
+
+
 def node_opts(opt) -> None:
     """Fill nodeIndex/numNodes/gpu from torchrun-style env when not given;
     export ``--commTimeout`` for the communicators."""

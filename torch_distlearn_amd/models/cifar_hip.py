@@ -382,7 +382,8 @@ class CifarHIPExecutor:
                 raise ValueError("DeviceLoader images do not match the model input")
             self.C.prep_step_gather(img, order, lab_all, lab_out, ctr, n_order, B, C, mean, std, self.x8.data_ptr(),
                                     self.kin0, h, h, SPAD, self.p32[0].data_ptr(), self.w1p.data_ptr(), self.couts[0],
-                                    KSIZE * KSIZE, self.cins_real[0], self.w1_cp, *tw, *self._zero_args(train), s)
+                                    KSIZE * KSIZE, self.cins_real[0], self.w1_cp, *tw, *self._zero_args(train), s,
+                                    x.augment_args() if hasattr(x, "augment_args") else None)
             return B
         B = x.shape[0]
         if B > self.cap:
@@ -811,7 +812,8 @@ class CifarHIPExecutor:
         lf = self._leaf(0, 0)
         return self.C.next_prep(img, order, lab_all, lab_out, ctr, n_order, loader.batch, C, mean, std,
                                 self.x8.data_ptr(), self.kin0, h, h, SPAD, *self._zero_args(True),
-                                self.w1p.data_ptr(), self.w1_cp, self.flat.offsets[lf] - HEADER, self.flat.numels[lf])
+                                self.w1p.data_ptr(), self.w1_cp, self.flat.offsets[lf] - HEADER, self.flat.numels[lf],
+                                loader.augment_args() if hasattr(loader, "augment_args") else None)
 
     def mark_prepared(self) -> None:
         """An update launch carrying :meth:`next_prep` is enqueued: the next forward_backward skips its prep."""
